@@ -6,11 +6,14 @@ NCC(9^3) + Grad('l2', loss_mult=2) (lambda=1), fp32, Adam lr 1e-4, synthetic U[0
 in HBM.  One step = forward + loss + backward + gradient all-reduce + Adam for `batch_per_gpu` pairs
 per rank (weak scaling: per-GPU work fixed as N grows).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the K steps and prints the
+headline fields; `--full` adds everything that takes runs of its own (per-kernel table and roofline, the other configurations and engines,
+the exchange timing of a multi-rank run, the recorded torch-ROCm baseline, the CPU baseline).  `--dump-outputs DIR` writes what the last
+timed step left behind (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -40,6 +43,13 @@ def parse():
                     help="diffeo_fp32 = BASELINE.json configs[2], the headline metric (default); dense_bf16 = configs[1]: int_steps=0, "
                          "MSE + 0.01 Grad, bf16 activations / fp32 accumulate under torch.autocast; diffeo_bf16 = the headline network "
                          "and losses with bf16 activations (an extra, labelled line: NOT the headline metric, which is fp32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the per-kernel pass (kernels, roofline), "
+                         "the extra configurations, the exchange timing (multi-rank), the torch-ROCm and CPU baselines; the --no-* options "
+                         "and --gpu-baseline below select among those and mean nothing without --full")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed (loss, gradient bucket, updated parameters and Adam "
+                         "moments) as DIR/<name>.npy, float32; inputs and initial weights are seeded, so two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true")                 # only the headline (profiling runs)
     ap.add_argument("--cpu-baseline-steps", type=int, default=2)               # timed CPU steps after one warm-up, at the FULL shape
@@ -367,7 +377,7 @@ def recorded_gpu_baseline():
             rec = json.load(f)
     except (OSError, ValueError):
         return None
-    rec["recorded"] = "%s (committed measurement of `bench.py --gpu-baseline`; not re-run in this invocation)" % os.path.relpath(files[-1], ROOT)
+    rec["recorded"] = "%s (committed measurement of `bench.py --full --gpu-baseline`; not re-run in this invocation)" % os.path.relpath(files[-1], ROOT)
     return rec
 
 
@@ -508,6 +518,20 @@ class Workload:
                 "(BASELINE.json configs[2])" % (sh, self.int_steps, self.B))
 
 
+def dump_outputs(wl, loss, directory):
+    """What a caller of the timed path holds after its last step, as <directory>/<name>.npy (float32, 5.2 MB at the default network): the loss
+    `Workload.step()` returned, the flat gradient bucket that step's backward filled (after the all-reduce on several ranks: the sum over
+    ranks), and what its Adam launch updated in place -- the parameters (every model parameter is a view of this buffer, in
+    `model.parameters()` order) and both moment estimates.  Nothing is sampled: the whole of each array is written."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.detach().reshape(()), "flat_grad": wl.opt.flat_grad, "flat_param": wl.opt.flat_param,
+              "exp_avg": wl.opt.exp_avg, "exp_avg_sq": wl.opt.exp_avg_sq}
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def timed_steps(wl, steps, vdist, dev, timer=None):
     """EXACTLY `steps` steps between barrier + synchronize on both sides; MAX over ranks.  timer: bracket every C-ABI launch
     with HIP events on the launch stream (per-kernel pass); None: nothing but the steps is inside the region (the `value` pass)."""
@@ -544,6 +568,7 @@ def timed_steps(wl, steps, vdist, dev, timer=None):
         "alloc_retries": ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
         "allocator_calls": ms1.get("allocation.all.allocated", 0) - ms0.get("allocation.all.allocated", 0),
         "reserved_gb": ms1.get("reserved_bytes.all.current", 0) / 1e9}
+    timed_steps.last_loss = loss
     return elapsed, float(loss.detach())
 
 
@@ -570,6 +595,26 @@ def ncc_valu_roofline(name, st, shape, B):
     ms = st["ms"] / st["launches"]
     return {"bound": "valu", "valu_wave_instructions_per_launch": instr, "valu_min_ms": min_ms, "valu_frac": min_ms / ms,
             "note": "vector-ALU issue roofline (4 cycles per wave-instruction, 1024 SIMDs, 2.4 GHz); the HBM figure (gbs) is kept for reference"}
+
+
+def per_kernel_pass(wl, steps, vdist, dev):
+    """Pass 2 of a --full run -- per-kernel table and `roofline`: every C-ABI launch bracketed by HIP events on the launch stream, the
+    full-resolution launches serialised (one kernel on the chip at a time, so that a launch's duration is its own), every launch on ONE
+    stream (the weight-gradient launches of the coarse levels too: a launch that shares the chip with the other stream's kernels would be
+    timed longer than rocprofv3's serial pass times it -- VERDICT round 4: 455 vs 387 us on the dominant kernel).
+    Returns (stats, steps of the pass, its elapsed seconds)."""
+    from voxelmorph_amd import profiler
+    from voxelmorph_amd.torch import functional as VF
+    keep_overlap = VF.OVERLAP_SMALL_LEVELS
+    VF.OVERLAP_SMALL_LEVELS = False
+    try:
+        wl.graphed.eager()                   # the capture emptied the caching allocator's pool: one eager step outside the pass re-populates it
+        timer = profiler.KernelTimer()
+        ksteps = min(steps, 10)
+        elapsed_k, _ = timed_steps(wl, ksteps, vdist, dev, timer)
+    finally:
+        VF.OVERLAP_SMALL_LEVELS = keep_overlap
+    return timer.resolve(), ksteps, elapsed_k
 
 
 def kernel_table(stats, steps, shape=None, B=1):
@@ -685,22 +730,16 @@ def main():
     elapsed, final_loss = timed_steps(wl, args.steps, vdist, dev)
     host_ms = timed_steps.host_enqueue_s / args.steps * 1e3
     submission = timed_steps.submission
-    # pass 2 -- per-kernel table and `roofline`: every C-ABI launch bracketed by HIP events on the launch stream, the full-resolution
-    # launches serialised (one kernel on the chip at a time, so that a launch's duration is its own)
-    # every launch on ONE stream (the weight-gradient launches of the coarse levels too: a launch that shares the chip with the other stream's
-    # kernels would be timed longer than rocprofv3's serial pass times it -- VERDICT round 4: 455 vs 387 us on the dominant kernel)
-    keep_overlap = VF.OVERLAP_SMALL_LEVELS
-    VF.OVERLAP_SMALL_LEVELS = False
-    wl.graphed.eager()                       # the capture emptied the caching allocator's pool: one eager step outside the pass re-populates it
-    timer = profiler.KernelTimer()
-    ksteps = min(args.steps, 10)
-    elapsed_k, _ = timed_steps(wl, ksteps, vdist, dev, timer)
-    VF.OVERLAP_SMALL_LEVELS = keep_overlap
-    stats = timer.resolve()
-    comm_ev = comm_evidence(wl.opt, dev) if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, timed_steps.last_loss, args.dump_outputs)
+    stats, ksteps, elapsed_k, comm_ev = None, 0, 0.0, None
+    if args.full:
+        stats, ksteps, elapsed_k = per_kernel_pass(wl, args.steps, vdist, dev)
+        comm_ev = comm_evidence(wl.opt, dev) if world > 1 else None
 
     extra = {}
-    if world == 1 and args.config == "diffeo_fp32" and not args.no_extra_configs:
+    if args.full and world == 1 and args.config == "diffeo_fp32" and not args.no_extra_configs:
+        keep_overlap = VF.OVERLAP_SMALL_LEVELS
         # the other BASELINE.json configs that fit one GPU, a few steps each, in the SAME line (labelled; none of them is `value`)
         del wl
         torch.cuda.empty_cache()
@@ -775,6 +814,22 @@ def main():
 
     if rank != 0:
         return
+    out = {
+        "metric": "volume-pairs/sec VxmDense 160x192x224 int_steps=0 MSE train (bf16 activations)" if dense
+                  else ("volume-pairs/sec VxmDense 160x192x224 int_steps=7 NCC train (bf16 activations; not the fp32 headline)" if bf16
+                        else "volume-pairs/sec VxmDense 160x192x224 int_steps=7 NCC train"),
+        "value": world * B * args.steps / elapsed, "unit": "volume-pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
+        "config": {"workload": wl_desc(args, shape, B), "global_batch": world * B, "parallelism": "dp%d" % world,
+                   "fp32_engine": VF.fp32_engine_note()},
+        "final_loss": final_loss,
+        "host_enqueue_ms_per_step": host_ms,        # rank 0's host time per step of the value pass (hipGraphLaunch, or Python + launches when eager), without the pacing wait
+        "submission": submission,                   # value pass: graph replays vs eager steps, caching-allocator activity inside the timed region
+    }
+    if not args.full:                               # the plain run: the headline and what its own timed steps left behind, nothing else
+        print(json.dumps(out))
+        return
     kernels = kernel_table(stats, ksteps, shape, B)
     dom = max(stats, key=lambda k: stats[k]["ms"])
     ds = stats[dom]
@@ -788,16 +843,8 @@ def main():
     st_bytes, st_ms = sum(stats[k]["bytes"] for k in stv), sum(stats[k]["ms"] for k in stv)
     # the same sum with the two ResizeTransform launches that remain (x0.5 forward / backward) -- what the round-5 verdict added up (604 us then)
     st_ms_rs = st_ms + sum(stats[k]["ms"] for k in stats if k.startswith("resize3d"))
-    out = {
-        "metric": "volume-pairs/sec VxmDense 160x192x224 int_steps=0 MSE train (bf16 activations)" if dense
-                  else ("volume-pairs/sec VxmDense 160x192x224 int_steps=7 NCC train (bf16 activations; not the fp32 headline)" if bf16
-                        else "volume-pairs/sec VxmDense 160x192x224 int_steps=7 NCC train"),
-        "value": world * B * args.steps / elapsed, "unit": "volume-pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
-        "config": {"workload": wl_desc(args, shape, B), "global_batch": world * B, "parallelism": "dp%d" % world,
-                   "fp32_engine": VF.fp32_engine_note()},
-        "roofline": roof, "kernels": kernels, "final_loss": final_loss,
+    out.update({
+        "roofline": roof, "kernels": kernels,
         # SpatialTransformer + VecInt against the HBM roofline (north star: >= 50 %); on the near-zero field of a random-init flow head --
         # extra_configs.diffeo_fp32_trained_flow carries the same figure on a 5-voxel field
         "spatial_transformer_plus_vecint": {"algorithmic_bytes_per_step": st_bytes / ksteps, "ms_per_step": st_ms / ksteps,
@@ -807,9 +854,7 @@ def main():
                                             "note": "round 6: fullsize + the final warp are one kernel, so the bytes are those of the FUSED formulation "
                                                     "(no full-resolution pos_flow: 667 MB per pair, was 719 + 372 of resize traffic); the fraction of a "
                                                     "fused path falls when bytes are removed faster than time -- compare ms_per_step_with_resize across rounds"},
-        "host_enqueue_ms_per_step": host_ms,        # rank 0's host time per step of the value pass (hipGraphLaunch, or Python + launches when eager), without the pacing wait
-        "submission": submission,                   # value pass: graph replays vs eager steps, caching-allocator activity inside the timed region
-    }
+    })
     cmu = conv_mfma_util(stats, "_bf16" if bf16 else "")
     if cmu is not None:
         out["conv_mfma_util"] = cmu

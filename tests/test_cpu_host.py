@@ -419,6 +419,18 @@ def test_bench_gpus_n_self_launches_one_rank_per_gpu():
     assert "WORLD_SIZE" not in out.stderr.split("bench.py needs an MI355X")[0][-300:]
 
 
+def test_bench_options_of_the_plain_and_the_full_run(monkeypatch):
+    """`--full` and `--dump-outputs DIR` exist and are off by default: a plain `bench.py --gpus 1 --steps N --warmup W` asks for neither."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    plain = bench.parse()
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7 and plain.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "d"])
+    both = bench.parse()
+    assert both.full is True and both.dump_outputs == "d"
+
+
 def test_bench_reports_the_roofline_that_binds_the_kernel():
     """bench.py prices a kernel against the roofline with the larger minimum time: the fp32 conv (119 GFLOP, 0.88 GB per launch) is an
     MFMA kernel; a 16-channel bf16 layer (0.095 TFLOP, 0.44 GB) is an HBM kernel whose MFMA fraction is kept beside; a 32-channel bf16

@@ -4,7 +4,8 @@
 * the two-rank data-parallel step (scripts/torch/train.py:151-154 replaced by one all-reduce of the flat bucket) run as two processes
   that SHARE the one GPU of the box: both ranks end on the same weights, and those are the weights of a one-process step on the
   concatenated batch (the oracle plays no part: the HIP kernels compute on every rank);
-* `bench.py --gpus 2` on the shared device: the line reports two ranks and names its exchange.
+* `bench.py --gpus 2` on the shared device: the line reports two ranks and names its exchange;
+* a plain `bench.py` run: the headline alone, and `--dump-outputs` leaves the arrays of its last timed step.
 """
 import json
 import os
@@ -217,13 +218,38 @@ def test_two_rank_step_on_the_shared_device_equals_one_process_on_the_concatenat
 def test_bench_two_ranks_on_the_shared_device(vxm):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VXM_SHARE_DEVICE="1", VXM_DIST_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3", "--shape", "32,48,32",
-                          "--no-extra-configs", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-extra-configs", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 2 and line["scaling"] == "weak"
     assert line["comm"]["ranks_seen"] == 2 and "gloo" in line["comm"]["backend"]
     assert line["submission"]["graph_replays"] == 3 and line["submission"]["device_allocs"] == 0
     assert line["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_step(vxm, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` line carries the headline of exactly N timed steps and nothing that takes runs of
+    its own (those are behind --full); `--dump-outputs DIR` leaves what the last timed step computed as float32 .npy files: finite, the
+    size of the flat bucket, the loss of the line, a gradient and Adam moments that the steps have really written."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "3", "--shape", "32,48,32",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["submission"]["graph_replays"] + line["submission"]["eager_steps"] == 3
+    assert line["unit"] == "volume-pairs/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3        # one pair per step
+    for key in ("kernels", "roofline", "extra_configs", "cpu_baseline", "gpu_baseline", "comm", "conv_mfma_util"):
+        assert key not in line, key
+    arrs = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert sorted(arrs) == ["exp_avg", "exp_avg_sq", "flat_grad", "flat_param", "loss"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+    n = arrs["flat_param"].size
+    assert all(arrs[k].shape == (n,) for k in ("flat_grad", "exp_avg", "exp_avg_sq")) and arrs["loss"].shape == ()
+    assert float(arrs["loss"]) == np.float32(line["final_loss"])
+    assert np.abs(arrs["flat_grad"]).max() > 0 and np.abs(arrs["exp_avg"]).max() > 0 and arrs["exp_avg_sq"].min() >= 0
 
 
 def test_range_report_separates_heavy_tails_from_ordinary_batches(vxm):
