@@ -40,7 +40,7 @@ typedef enum {
 enum { VXM_INTERP_LINEAR = 0, VXM_INTERP_NEAREST = 1 };   /* SpatialTransformer mode, layers.py:11 */
 enum { VXM_PENALTY_L1 = 0, VXM_PENALTY_L2 = 1 };          /* Grad penalty, losses.py:98 */
 
-int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 501 = 0.5.1 (round 6; every 0.4 / 0.5.0 entry point kept) */
+int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 502 = 0.5.2 (round 6; every 0.4 / 0.5.x entry point kept) */
 const char* vxm_last_error_string(void);
 
 /* ---- the two umbrella names SURVEY.md section 8b lists.  Every op has its own *_workspace_bytes() query next to it; this one dispatches
@@ -105,6 +105,11 @@ int vxm_resize3d_fwd(const float* x, float* out, int B, int C, int D, int H, int
                      float factor, void* stream);
 int vxm_resize3d_bwd(const float* gout, float* gx, int B, int C, int D, int H, int W, int oD, int oH, int oW,
                      float factor, void* stream);
+/* which kernel vxm_resize3d_bwd runs for these extents (tests, profiles; the same function makes the choice in both): 0 = k_resize3d_bwd
+ * (scatter with atomics), 1 = k_resize3d_bwd_gather_tiled, 2 = k_resize3d_bwd_down, 3 = k_resize3d_bwd_sep, 4 = k_resize3d_bwd_march;
+ * -1 for extents vxm_resize3d_bwd rejects.  Decided by the fp32 ratios (in - 1) / (out - 1) of the three axes (and VXM_RESIZE_BWD=sep,
+ * read once per process, which takes march and down out of the choice). */
+int vxm_resize3d_bwd_kernel(int D, int H, int W, int oD, int oH, int oW);
 
 /* ---- ConvBlock / flow conv, networks.py:299-305,211,257: 3x3x3, stride 1, pad 1 conv + bias +
  * LeakyReLU(act_slope) (act_slope = 1 -> no activation).  fp32 MFMA implicit GEMM.

@@ -60,6 +60,26 @@ def test_kernels_are_gfx950_only():
     assert archs == {b"gfx950"}, archs
 
 
+def test_resize_backward_kernel_choice_table():
+    """vxm_resize3d_bwd_kernel (the function vxm_resize3d_bwd itself dispatches on) for every case of tests/resize_cases.py: the fp32
+    thresholds on (in - 1) / (out - 1) send each shape to the kernel the GPU tests validate it on.  A threshold that changes fails here; the
+    shape does not move to another kernel and lose its coverage.  Every code is reached; extents the backward rejects give -1."""
+    import resize_cases as rc
+    h = _lib.lib()
+    assert h.vxm_version() >= 502
+    sep_switch = os.environ.get("VXM_RESIZE_BWD", "")[:1] == "s"         # read once per process by the library: march and down leave the choice
+    seen = set()
+    for name, inp, vel, out, code in rc.CASES:
+        assert rc.out_shape(inp, vel) == out, name
+        if sep_switch:
+            code = {rc.MARCH: rc.SEP, rc.DOWN: rc.GATHER_TILED}.get(code, code)
+        got = h.vxm_resize3d_bwd_kernel(*inp, *out)
+        assert got == code, "%s: %s -> %s runs %s, the table says %s" % (name, inp, out, rc.KERNELS[got], rc.KERNELS[code])
+        seen.add(got)
+    assert sep_switch or seen == set(range(5))
+    assert h.vxm_resize3d_bwd_kernel(1, 8, 8, 2, 16, 16) == -1 and h.vxm_resize3d_bwd_kernel(8, 8, 8, 0, 4, 4) == -1
+
+
 def test_no_cpu_fallback():
     st = vxm.layers.SpatialTransformer((8, 8, 8))
     with pytest.raises(_lib.VxmHipError, match="no CPU fallback"):

@@ -14,6 +14,8 @@ import torch
 from oracle import c_oracle
 from oracle import vxm_oracle as orc
 
+import resize_cases as rc           # tests/resize_cases.py: the resize table, shared with test_cpu_host.py and tools/resize_gates.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -262,6 +264,14 @@ NCC_GRAD_GATE = 2.5e-6
 NCC_GRAD_GATE_REF = 1.5e-5
 NCC_GRAD_GATE_1D = 1e-4
 NCC_LOSS_GATE, NCC_LOSS_GATE_REF = 2.5e-7, 2.5e-6
+# Resize gates (test_resize_every_backward_kernel_vs_fp64, test_resize_planar_vs_fp64): NOT from what the kernels give -- 4 x the largest error
+# of the REFERENCE's own fp32 evaluation (ATen forward and autograd on the CPU) against the float64 arbiter over the cases of
+# tests/resize_cases.py, on the tests' inputs (`python tools/resize_gates.py` prints them; profiles/pr02_resize_gates_cpu.txt).  ATen forms
+# `ratio * dst` in fp32, so its weights sit ~1e-6 from the fp64 ones: the kernels reproduce that arithmetic and may reorder the sums, no more.
+#   3-D  forward rel-L2 2.948e-6 -> 1.179e-5;  backward rel-L2 2.884e-6 -> 1.153e-5;  adjoint gap |<y,g> - <x,gx>| / (|y| |g|) 2.179e-9 -> 8.71e-9
+#   2-D  forward        1.868e-6 -> 7.47e-6;   backward        1.846e-6 -> 7.38e-6;   adjoint gap                              1.179e-8 -> 4.71e-8
+RESIZE_FWD_GATE, RESIZE_BWD_GATE, RESIZE_ADJ_GATE = 1.179e-5, 1.153e-5, 8.71e-9
+RESIZE2D_FWD_GATE, RESIZE2D_BWD_GATE, RESIZE2D_ADJ_GATE = 7.47e-6, 7.38e-6, 4.71e-8
 
 
 def test_ncc_golden(vxm, g_losses):
@@ -1203,6 +1213,116 @@ def test_resize_upsampling_backward_marching_kernel_vs_oracle(vxm, low, BC):
     xg.grad = None
     vxm.layers.ResizeTransform(0.5, 3)(xg).backward(G(g))
     assert np.array_equal(first, N(xg.grad))
+
+
+_RESIZE_REF = {}
+
+
+def _resize_reference(key, x, g, vel):
+    """float64 arbiter of one case (oracle.resize_transform and its autograd), computed once per process and left unchanged"""
+    if key not in _RESIZE_REF:
+        xd = torch.from_numpy(x).double().requires_grad_()
+        y = orc.resize_transform(xd, vel)
+        y.backward(torch.from_numpy(g).double())
+        _RESIZE_REF[key] = (y.detach().numpy(), xd.grad.numpy())
+    return _RESIZE_REF[key]
+
+
+def _resize_switch_is_sep():
+    return os.environ.get("VXM_RESIZE_BWD", "")[:1] == "s"
+
+
+@pytest.mark.parametrize("case", rc.CASES, ids=rc.IDS)
+def test_resize_every_backward_kernel_vs_fp64(vxm, case):
+    """Each of the five kernels vxm_resize3d_bwd chooses between (and the one forward kernel) at the edges of its range -- ratios away from
+    1/2, several tiles and depth blocks, ragged tiles, odd extents, an LDS block that does not fit, output axes of extent 1, input voxels
+    no output names -- against the float64 evaluation of the reference's ResizeTransform; gates from the reference's own fp32 error
+    (RESIZE_* above).  The kernel the dispatcher picks is asserted first: a threshold that moves fails here, it does not move a shape to
+    another kernel unseen.  Under VXM_RESIZE_BWD=sep (test_resize_backward_sep_switch_in_subprocess) march shapes run sep, down shapes
+    gather_tiled."""
+    from voxelmorph_amd import _lib
+    name, inp, vel, out, code = case
+    if _resize_switch_is_sep():
+        code = {rc.MARCH: rc.SEP, rc.DOWN: rc.GATHER_TILED}.get(code, code)
+    assert _lib.lib().vxm_resize3d_bwd_kernel(*inp, *out) == code
+    tag = "resize %s [%s]" % (name, rc.KERNELS[code])
+    x, g = rc.arrays(case)
+    assert g.shape[2:] == out
+    y64, gx64 = _resize_reference(name, x, g, vel)
+    layer = vxm.layers.ResizeTransform(vel, 3)
+    xg = G(x, True)
+    y = layer(xg)
+    assert tuple(y.shape) == g.shape
+    factor = 1.0 / vel
+    np.testing.assert_allclose(N(y), c_oracle.resize3d(x, vel), atol=5e-6 * max(1.0, factor), rtol=0)
+    gate(tag + " forward vs fp64", rel_l2(N(y), y64), RESIZE_FWD_GATE)
+    y.backward(G(g))
+    gx = N(xg.grad).copy()
+    gate(tag + " backward vs fp64", rel_l2(gx, gx64), RESIZE_BWD_GATE)
+    gate(tag + " adjoint <y,g> - <x,gx>", rc.adjoint_gap(N(y), g, x, gx), RESIZE_ADJ_GATE)
+    if code != rc.SCATTER:                                        # documented as deterministic: no atomics
+        xg.grad = None
+        layer(xg).backward(G(g))
+        assert torch.equal(xg.grad.cpu(), torch.from_numpy(gx)), tag + ": two backward runs differ"
+    if name in rc.SKIPPING:
+        # voxels no output names: exactly 0 (written, not left uninitialised), and a NaN in one gradient voxel reaches the voxels the
+        # reference's fp32 autograd carries it to (the up to 8 that output names, one with weight 0 where the source coordinate is an
+        # integer) and no other -- a kernel that multiplies a clamped load by a zero weight spreads it
+        ones = torch.from_numpy(x).requires_grad_()
+        orc.resize_transform(ones, vel).backward(torch.ones(g.shape))
+        unnamed = ones.grad.numpy() == 0
+        assert unnamed.sum() > x.size // 2 and np.all(gx[unnamed] == 0)
+        gn = g.copy()
+        gn[0, 1, out[0] // 2, out[1] // 2, out[2] // 2] = np.nan
+        xr = torch.from_numpy(x).requires_grad_()
+        orc.resize_transform(xr, vel).backward(torch.from_numpy(gn))
+        want = np.isnan(xr.grad.numpy())
+        xg.grad = None
+        layer(xg).backward(G(gn))
+        got = N(xg.grad)
+        assert 1 <= want.sum() <= 8
+        assert np.array_equal(np.isnan(got), want), "%s: NaN voxels %s, the reference's %s" % (tag, np.argwhere(np.isnan(got)).tolist(), np.argwhere(want).tolist())
+        assert np.all(got[unnamed & ~want] == 0)
+
+
+def test_resize_backward_sep_switch_in_subprocess():
+    """VXM_RESIZE_BWD=sep (read once per process, hence the fresh child) takes the marching kernel out of the choice: the three march rows
+    of the table run k_resize3d_bwd_sep -- (9,17,33) on tiles that all fit its LDS block -- against the same fp64 gradient and gates."""
+    import subprocess
+    import sys
+    env = dict(os.environ, VXM_RESIZE_BWD="sep")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-s", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"),
+                        "-k", "test_resize_every_backward_kernel_vs_fp64 and march"],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=120)
+    print("\n".join(line for line in r.stdout.splitlines() if line.startswith("[gate]")))
+    assert r.returncode == 0 and "3 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("vel", rc.PLANAR_VELS, ids=["vel0.8", "vel1/3", "vel3", "vel1.5"])
+@pytest.mark.parametrize("shape", rc.PLANAR_SHAPES, ids=["13x37", "2x9"])
+def test_resize_planar_vs_fp64(vxm, shape, vel):
+    """ResizeTransform(vel, 2) (k_resize2d_fwd / k_resize2d_bwd, a scatter: no repeatability to assert) against the float64 oracle: forward,
+    backward and the adjoint identity at odd extents, two rows, an output of one row (2 rows x 1/1.5), and the case with NO output row
+    (2 rows x 1/3), which the reference refuses and the product must refuse too."""
+    from voxelmorph_amd import _lib
+    x, g = rc.planar_arrays(shape, vel)
+    layer = vxm.layers.ResizeTransform(vel, 2)
+    if g is None:
+        with pytest.raises(RuntimeError):
+            orc.resize_transform(torch.from_numpy(x), vel)
+        with pytest.raises(_lib.VxmHipError, match="bad output shape"):
+            layer(G(x))
+        return
+    tag = "resize 2-D %s vel_resize %.3g" % (shape, vel)
+    y64, gx64 = _resize_reference(("2d", shape, vel), x, g, vel)
+    xg = G(x, True)
+    y = layer(xg)
+    assert tuple(y.shape) == g.shape
+    gate(tag + " forward vs fp64", rel_l2(N(y), y64), RESIZE2D_FWD_GATE)
+    y.backward(G(g))
+    gate(tag + " backward vs fp64", rel_l2(N(xg.grad), gx64), RESIZE2D_BWD_GATE)
+    gate(tag + " adjoint <y,g> - <x,gx>", rc.adjoint_gap(N(y), g, x, N(xg.grad)), RESIZE2D_ADJ_GATE)
 
 
 # ------------------------------------------------------------------ full benchmark size (160x192x224): properties

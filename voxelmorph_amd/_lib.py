@@ -45,6 +45,7 @@ SIGNATURES = {
     "vxm_vecint_bwd_ws": [_P, _P, _P, _P, _P, _S, _I, _I, _I, _I, _I, _P],
     "vxm_resize3d_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "vxm_resize3d_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "vxm_resize3d_bwd_kernel": [_I, _I, _I, _I, _I, _I],
     "vxm_conv3d_k3_packed_elems": [_I, _I],
     "vxm_conv3d_k3_pack_weights": [_P, _P, _I, _I, _I, _P],
     "vxm_conv3d_k3_pack_weights_range": [_P, _P, _I, _I, _I, _I, _I, _P],

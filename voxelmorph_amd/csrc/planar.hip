@@ -332,8 +332,8 @@ int vxm_vecint2d_bwd(const float* vec, const float* steps, const float* gout, fl
 
 int vxm_resize2d_fwd(const float* x, float* out, int B, int C, int H, int W, int oH, int oW, float factor, void* stream) {
     if (int e = check_plane("vxm_resize2d_fwd", B, C, H, W)) return e;
-    VXM_REQUIRE(x && out, VXM_ERR_NULL_POINTER, "vxm_resize2d_fwd: null pointer");
     VXM_REQUIRE(oH > 0 && oW > 0 && factor > 0.0f && (long long)B * C <= 65535, VXM_ERR_BAD_SHAPE, "vxm_resize2d_fwd: bad output shape %dx%d / factor %g", oH, oW, factor);
+    VXM_REQUIRE(x && out, VXM_ERR_NULL_POINTER, "vxm_resize2d_fwd: null pointer");
     const float rh = oH > 1 ? (float)(H - 1) / (float)(oH - 1) : 0.0f, rw = oW > 1 ? (float)(W - 1) / (float)(oW - 1) : 0.0f;
     hipLaunchKernelGGL(k_resize2d_fwd, dim3(vxm_blocks((long long)oH * oW, 256), B * C), dim3(256), 0, VXM_STREAM(stream), x, out, H, W, oH, oW,
                        rh, rw, factor > 1.0f ? factor : 1.0f, factor < 1.0f ? factor : 1.0f);
@@ -342,8 +342,8 @@ int vxm_resize2d_fwd(const float* x, float* out, int B, int C, int H, int W, int
 
 int vxm_resize2d_bwd(const float* gout, float* gx, int B, int C, int H, int W, int oH, int oW, float factor, void* stream) {
     if (int e = check_plane("vxm_resize2d_bwd", B, C, H, W)) return e;
-    VXM_REQUIRE(gout && gx, VXM_ERR_NULL_POINTER, "vxm_resize2d_bwd: null pointer");
     VXM_REQUIRE(oH > 0 && oW > 0 && factor > 0.0f && (long long)B * C <= 65535, VXM_ERR_BAD_SHAPE, "vxm_resize2d_bwd: bad output shape %dx%d / factor %g", oH, oW, factor);
+    VXM_REQUIRE(gout && gx, VXM_ERR_NULL_POINTER, "vxm_resize2d_bwd: null pointer");
     const float rh = oH > 1 ? (float)(H - 1) / (float)(oH - 1) : 0.0f, rw = oW > 1 ? (float)(W - 1) / (float)(oW - 1) : 0.0f;
     (void)hipMemsetAsync(gx, 0, sizeof(float) * (size_t)B * C * H * W, VXM_STREAM(stream));
     hipLaunchKernelGGL(k_resize2d_bwd, dim3(vxm_blocks((long long)oH * oW, 256), B * C), dim3(256), 0, VXM_STREAM(stream), gout, gx, H, W, oH, oW,

@@ -548,8 +548,11 @@ __global__ void __launch_bounds__(256) k_resize3d_bwd(const float* __restrict__ 
 // most floor(2/ratio)+1 consecutive outputs; the KC candidates starting one below floor((i-1)/ratio)
 // are a superset and each is re-evaluated with the forward's exact index/lambda arithmetic.
 constexpr int RS_KC = 7;
-__device__ __forceinline__ void axis_taps(int i, float ratio, int n_in, int n_out, int& olo, float (&w)[RS_KC]) {
+// `named`: bit k set when candidate k NAMES voxel i -- the forward reads it there, possibly with weight 0 (a source coordinate that is an integer
+// gives l1 = 0 at i1); upsample_trilinear3d_backward adds to exactly those voxels, so a NaN / Inf gradient reaches them and no other
+__device__ __forceinline__ void axis_taps_named(int i, float ratio, int n_in, int n_out, int& olo, float (&w)[RS_KC], int& named) {
     olo = ratio > 0.0f ? max(0, (int)floorf((float)(i - 1) / ratio) - 1) : 0;
+    named = 0;
 #pragma unroll
     for (int k = 0; k < RS_KC; ++k) {
         const int o = olo + k;
@@ -558,7 +561,12 @@ __device__ __forceinline__ void axis_taps(int i, float ratio, int n_in, int n_ou
         lin_src(min(o, n_out - 1), ratio, n_in, i0, i1, l0, l1);
         const float wt = (i0 == i ? l0 : 0.0f) + (i1 == i ? l1 : 0.0f);
         w[k] = o < n_out ? wt : 0.0f;
+        named |= (o < n_out && (i0 == i || i1 == i)) ? 1 << k : 0;
     }
+}
+__device__ __forceinline__ void axis_taps(int i, float ratio, int n_in, int n_out, int& olo, float (&w)[RS_KC]) {
+    int named;
+    axis_taps_named(i, ratio, n_in, n_out, olo, w, named);
 }
 
 // ---- tiled forms: a block owns a 4 x 8 x 32 (D x H x W) tile, its 44 per-axis interpolation records are computed
@@ -679,13 +687,13 @@ __global__ void __launch_bounds__(256) k_resize3d_bwd_gather_tiled(const float* 
 
 // ---- adjoint of a DOWN-sampling resize (every ratio >= 1: an input voxel is named by at most two outputs per axis, and by none when the
 // ratio skips it): the gather above with its loops resolved -- two taps per axis from the same axis_taps() records, eight unconditional
-// loads per voxel (clamped addresses, weight zero where a tap does not exist), same a -> e -> c summation order.  The general kernel ran
+// loads per voxel (a tap that does not name the voxel loads 0.0 through an out-of-range offset), same a -> e -> c summation order.  The general kernel ran
 // its three data-dependent loops at 47 us for the 10 -> 83 MB of the headline field (k_resize3d_bwd_gather_tiled, 2.0 TB/s).
 __global__ void __launch_bounds__(256) k_resize3d_bwd_down(const float* __restrict__ gout, float* __restrict__ gx, int D, int H, int W, int oD, int oH,
                                                            int oW, float rd, float rh, float rw, float scale) {
     // 16 depths per block (the 44 + 12 axis records cost as much as four voxels of a thread: amortised over sixteen)
     constexpr int RD_D = 16, RD_N = RT_W + RT_H + RD_D;
-    __shared__ int so[RD_N];
+    __shared__ int so[RD_N], sm0[RD_N], sm1[RD_N];                             // first tap; per tap 0, or VXM_OOB when it does not name the voxel
     __shared__ float s0[RD_N], s1[RD_N];
     const int tw_ = (W + RT_W - 1) / RT_W, th_ = (H + RT_H - 1) / RT_H;
     int t_ = blockIdx.x;
@@ -699,13 +707,17 @@ __global__ void __launch_bounds__(256) k_resize3d_bwd_down(const float* __restri
         const int n_in = ax == 2 ? W : (ax == 1 ? H : D), n_out = ax == 2 ? oW : (ax == 1 ? oH : oD);
         int olo;
         float wt[RS_KC];
-        axis_taps(min(i, n_in - 1), ax == 2 ? rw : (ax == 1 ? rh : rd), n_in, n_out, olo, wt);
+        int named;
+        axis_taps_named(min(i, n_in - 1), ax == 2 ? rw : (ax == 1 ? rh : rd), n_in, n_out, olo, wt, named);
+        // the outputs that name this voxel: at most two, neighbours (ratio >= 1).  Only those are loaded: 0 x a clamped load carried a NaN / Inf
+        // of one gradient voxel to voxels the forward never read, the ones a ratio >= 2 skips among them
         int klo = 0;
-        while (klo < RS_KC - 2 && wt[klo] == 0.0f) ++klo;                      // first tap that counts; at most one more follows (ratio >= 1)
+        while (klo < RS_KC - 2 && !((named >> klo) & 1)) ++klo;                // first tap that names the voxel; at most one more follows
         float a = 0.0f, b = 0.0f;
 #pragma unroll
         for (int j = 0; j < RS_KC; ++j) { a = j == klo ? wt[j] : a; b = j == klo + 1 ? wt[j] : b; }
         so[tid] = min(olo + klo, n_out - 1); s0[tid] = a; s1[tid] = olo + klo + 1 < n_out ? b : 0.0f;
+        sm0[tid] = (named >> klo) & 1 ? 0 : VXM_OOB; sm1[tid] = (named >> klo) & 2 ? 0 : VXM_OOB;
     }
     __syncthreads();
     const int tx = tid & 31, ty = tid >> 5;
@@ -716,6 +728,9 @@ __global__ void __launch_bounds__(256) k_resize3d_bwd_down(const float* __restri
     const int ow0 = so[tx], ow1 = min(ow0 + 1, oW - 1), oh0 = so[RT_W + ty], oh1 = min(oh0 + 1, oH - 1);
     const float wc[2] = {s0[tx], s1[tx]}, we[2] = {s0[RT_W + ty], s1[RT_W + ty]};
     const int col[2] = {ow0, ow1}, row[2] = {oh0 * oW, oh1 * oW};
+    int mhw[4];                                                                // OR-ed into a load's byte offset: out of range unless all three taps name the voxel
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mhw[j] = (j & 2 ? sm1[RT_W + ty] : sm0[RT_W + ty]) | (j & 1 ? sm1[tx] : sm0[tx]);
     float* o = gx + bc * (size_t)D * H * W;
 #pragma unroll 4
     for (int dd = 0; dd < RD_D; ++dd) {
@@ -724,9 +739,10 @@ __global__ void __launch_bounds__(256) k_resize3d_bwd_down(const float* __restri
         const int od0 = so[RT_W + RT_H + dd], od1 = min(od0 + 1, oD - 1);
         const float wa[2] = {s0[RT_W + RT_H + dd], s1[RT_W + RT_H + dd]};
         const int pl[2] = {od0 * oH * oW, od1 * oH * oW};
+        const int ma[2] = {sm0[RT_W + RT_H + dd], sm1[RT_W + RT_H + dd]};
         float g[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) g[k] = vxm_bload(rg, (pl[k >> 2] + row[(k >> 1) & 1] + col[k & 1]) << 2, 0);
+        for (int k = 0; k < 8; ++k) g[k] = vxm_bload(rg, (pl[k >> 2] + row[(k >> 1) & 1] + col[k & 1]) << 2 | ma[k >> 2] | mhw[k & 3], 0);
         float acc = 0.0f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc += (wa[k >> 2] * we[(k >> 1) & 1]) * wc[k & 1] * g[k];
@@ -1315,16 +1331,35 @@ int vxm_resize3d_fwd(const float* x, float* out, int B, int C, int D, int H, int
     return vxm_check_launch("vxm_resize3d_fwd");
 }
 
+// The ONE place that picks the backward kernel (vxm_resize3d_bwd launches what this returns, vxm_resize3d_bwd_kernel reports it): per-axis
+// ratios (in - 1) / (out - 1) in fp32; an output axis of extent 1 has ratio 0 and counts as 1.0 in the minimum.
+enum { RBK_SCATTER = 0, RBK_GATHER = 1, RBK_DOWN = 2, RBK_SEP = 3, RBK_MARCH = 4 };
+static int resize_bwd_choice(int D, int H, int W, int oD, int oH, int oW, float& rd, float& rh, float& rw) {
+    rd = oD > 1 ? (float)(D - 1) / (float)(oD - 1) : 0.0f; rh = oH > 1 ? (float)(H - 1) / (float)(oH - 1) : 0.0f;
+    rw = oW > 1 ? (float)(W - 1) / (float)(oW - 1) : 0.0f;
+    const float rmin = fminf(oD > 1 ? rd : 1.0f, fminf(oH > 1 ? rh : 1.0f, oW > 1 ? rw : 1.0f));
+    const float rmax = fmaxf(rd, fmaxf(rh, rw));
+    static const bool use_march = [] { const char* e = getenv("VXM_RESIZE_BWD"); return !(e && e[0] == 's'); }();      // VXM_RESIZE_BWD=sep: the round-3 kernel (A/B)
+    if (use_march && rmin >= 0.47f && rmax < 0.75f) return RBK_MARCH;      // up-sampling by ~2: one thread per input voxel marching through the output planes
+    if (rmin > 0.4f && rmax < 0.75f) return RBK_SEP;                       // separable passes through LDS
+    if (use_march && rmin >= 1.0f) return RBK_DOWN;                        // down-sampling: at most two outputs per axis name an input voxel
+    if (rmin > 0.4f) return RBK_GATHER;                                    // floor(2/ratio) + 3 <= RS_KC: every contributing output is among the candidates
+    return RBK_SCATTER;                                                    // very large upsampling factors: scatter with atomics
+}
+
+int vxm_resize3d_bwd_kernel(int D, int H, int W, int oD, int oH, int oW) {
+    if (D < 2 || H < 2 || W < 2 || oD < 1 || oH < 1 || oW < 1) return -1;
+    float rd, rh, rw;
+    return resize_bwd_choice(D, H, W, oD, oH, oW, rd, rh, rw);
+}
+
 int vxm_resize3d_bwd(const float* gout, float* gx, int B, int C, int D, int H, int W, int oD, int oH, int oW, float factor,
                      void* stream) {
     if (int e = resize_args("vxm_resize3d_bwd", B, C, D, H, W, oD, oH, oW, factor)) return e;
     VXM_REQUIRE(gout && gx, VXM_ERR_NULL_POINTER, "vxm_resize3d_bwd: null pointer");
-    const float rd = oD > 1 ? (float)(D - 1) / (float)(oD - 1) : 0.0f, rh = oH > 1 ? (float)(H - 1) / (float)(oH - 1) : 0.0f,
-                rw = oW > 1 ? (float)(W - 1) / (float)(oW - 1) : 0.0f;
-    const float rmin = fminf(oD > 1 ? rd : 1.0f, fminf(oH > 1 ? rh : 1.0f, oW > 1 ? rw : 1.0f));
-    const float rmax = fmaxf(rd, fmaxf(rh, rw));
-    static const bool use_march = [] { const char* e = getenv("VXM_RESIZE_BWD"); return !(e && e[0] == 's'); }();      // VXM_RESIZE_BWD=sep: the round-3 kernel (A/B)
-    if (use_march && rmin >= 0.47f && rmax < 0.75f) {      // up-sampling by ~2: one thread per input voxel marching through the output planes
+    float rd, rh, rw;
+    const int kern = resize_bwd_choice(D, H, W, oD, oH, oW, rd, rh, rw);
+    if (kern == RBK_MARCH) {
         const int tiles2 = ((W + RM_W - 1) / RM_W) * ((H + RM_H - 1) / RM_H);
         int nseg = (1024 + tiles2 * B * C - 1) / (tiles2 * B * C);          // ~1000 blocks; a segment re-reads 3 - 4 output planes of its neighbour
         nseg = nseg < 1 ? 1 : nseg;
@@ -1333,7 +1368,7 @@ int vxm_resize3d_bwd(const float* gout, float* gx, int B, int C, int D, int H, i
         nseg = (D + seg_len - 1) / seg_len;
         hipLaunchKernelGGL(k_resize3d_bwd_march, dim3((unsigned)(tiles2 * nseg), B * C), dim3(256), 0, VXM_STREAM(stream),
                            gout, gx, D, H, W, oD, oH, oW, rd, rh, rw, factor, seg_len);
-    } else if (rmin > 0.4f && rmax < 0.75f) {      // separable passes through LDS
+    } else if (kern == RBK_SEP) {
         const long long tiles = (long long)((W + RB_W - 1) / RB_W) * ((H + RB_H - 1) / RB_H) * ((D + RB_D - 1) / RB_D);
         VXM_REQUIRE(tiles < (1ll << 31), VXM_ERR_BAD_SHAPE, "vxm_resize3d_bwd: too many tiles");
         constexpr int lds = (RB_SD * RB_SH * RB_SW + RB_SD * RB_SH * RB_W + RB_N * (RS_KC + 1) + RB_N) * 4;
@@ -1344,17 +1379,17 @@ int vxm_resize3d_bwd(const float* gout, float* gx, int B, int C, int D, int H, i
         (void)attr;
         hipLaunchKernelGGL(k_resize3d_bwd_sep, dim3((unsigned)tiles, B * C), dim3(RB_THREADS), lds, VXM_STREAM(stream),
                            gout, gx, D, H, W, oD, oH, oW, rd, rh, rw, factor);
-    } else if (use_march && rmin >= 1.0f) {      // down-sampling: at most two outputs per axis name an input voxel
+    } else if (kern == RBK_DOWN) {
         const long long tiles = (long long)((W + RT_W - 1) / RT_W) * ((H + RT_H - 1) / RT_H) * ((D + 15) / 16);
         VXM_REQUIRE(tiles < (1ll << 31), VXM_ERR_BAD_SHAPE, "vxm_resize3d_bwd: too many tiles");
         hipLaunchKernelGGL(k_resize3d_bwd_down, dim3((unsigned)tiles, B * C), dim3(256), 0, VXM_STREAM(stream),
                            gout, gx, D, H, W, oD, oH, oW, rd, rh, rw, factor);
-    } else if (rmin > 0.4f) {       // floor(2/ratio) + 3 <= RS_KC: every contributing output is among the candidates
+    } else if (kern == RBK_GATHER) {
         const long long tiles = (long long)((W + RT_W - 1) / RT_W) * ((H + RT_H - 1) / RT_H) * ((D + RT_D - 1) / RT_D);
         VXM_REQUIRE(tiles < (1ll << 31), VXM_ERR_BAD_SHAPE, "vxm_resize3d_bwd: too many tiles");
         hipLaunchKernelGGL(k_resize3d_bwd_gather_tiled, dim3((unsigned)tiles, B * C), dim3(256), 0, VXM_STREAM(stream),
                            gout, gx, D, H, W, oD, oH, oW, rd, rh, rw, factor);
-    } else {                 // very large upsampling factors: scatter with atomics
+    } else {                 // RBK_SCATTER
         (void)hipMemsetAsync(gx, 0, sizeof(float) * (size_t)B * C * D * H * W, VXM_STREAM(stream));
         hipLaunchKernelGGL(k_resize3d_bwd, dim3(vxm_blocks((long long)oD * oH * oW, 256), B * C), dim3(256), 0, VXM_STREAM(stream),
                            gout, gx, D, H, W, oD, oH, oW, rd, rh, rw, factor);
