@@ -464,6 +464,81 @@ def warp_explicit(src, flow, mode="bilinear"):
     return out
 
 
+def warp_arbiter(src, flow, gout=None):
+    """float64 arbiter of SpatialTransformer (2-D / 3-D, linear) that resolves `floor` where the reference does: the source coordinates are
+    the reference's fp32 operation chain (`_src_coords_explicit`), promoted to float64; the floor, the weights (x0 + 1 - x) and (x - x0),
+    the corner sums and zero padding (an outside corner is SKIPPED, never loaded) are float64.  Plain float64 grid_sample is the wrong
+    arbiter of d out / d flow: the derivative jumps at lattice points and fp32 / fp64 coordinates fall on different sides of them.
+    A non-finite coordinate has every corner outside (what ATen's integer conversion makes of it).  Returns (out, gsrc, gflow), the
+    gradients None without `gout`: gsrc the scatter of gout * weight, gflow_a = sum_c sum_corners sign_a prod_{b != a} w_b src[corner] gout."""
+    f64 = np.float64
+    src = np.asarray(src, dtype=f64)
+    B, C = src.shape[:2]
+    size = src.shape[2:]
+    nd = len(size)
+    xs = [np.asarray(x, dtype=f64) for x in _src_coords_explicit(flow)]
+    fin = np.ones(xs[0].shape, dtype=bool)
+    for x in xs:
+        fin &= np.isfinite(x)
+    xs = [np.where(fin, x, -2.0) for x in xs]
+    x0 = [np.floor(x) for x in xs]
+    wts = [(f + 1.0 - x, x - f) for x, f in zip(xs, x0)]
+    out = np.zeros((B, C) + tuple(size), dtype=f64)
+    out_t, src_t = np.moveaxis(out, 1, -1), np.moveaxis(src, 1, -1)          # channels last: one fancy index names a voxel's C values
+    if gout is not None:
+        gout_t = np.moveaxis(np.asarray(gout, dtype=f64), 1, -1)
+        gsrc = np.zeros_like(src)
+        gsrc_t = np.moveaxis(gsrc, 1, -1)
+        gflow = np.zeros((B, nd) + tuple(size), dtype=f64)
+    for corner in range(2 ** nd):
+        bits = [(corner >> (nd - 1 - a)) & 1 for a in range(nd)]
+        ok = fin.copy()
+        js = []
+        for a in range(nd):
+            j = x0[a] + bits[a]
+            ok &= (j >= 0) & (j <= size[a] - 1)
+            js.append(np.clip(j, 0, size[a] - 1).astype(np.int64))
+        sel = np.nonzero(ok)                                                   # (b, *voxel) of the samples this corner exists for
+        at = (sel[0],) + tuple(j[sel] for j in js)                             # (b, *corner voxel)
+        wa = [wts[a][bits[a]][sel] for a in range(nd)]
+        w = np.prod(wa, axis=0)
+        vals = src_t[at]                                                       # [n, C]
+        out_t[sel] += vals * w[:, None]
+        if gout is not None:
+            g = gout_t[sel]
+            np.add.at(gsrc_t, at, g * w[:, None])
+            s = (vals * g).sum(axis=1)
+            for a in range(nd):
+                wo = np.prod([wa[b] for b in range(nd) if b != a], axis=0) if nd > 1 else 1.0
+                gflow[(sel[0], a) + tuple(sel[1:])] += (1.0 if bits[a] else -1.0) * wo * s
+    return (out, gsrc, gflow) if gout is not None else (out, None, None)
+
+
+def vecint_arbiter(vec, nsteps, gout=None, fields=None):
+    """float64 arbiter of VecInt (any nsteps >= 1) with the same idea per step: the field every step samples AND samples at is an fp32 one --
+    by default the reference's (v_0 = vec * 2^-nsteps, v_{k+1} = v_k + transformer(v_k, v_k) in float32, layers.py:64-68), or `fields`, the
+    nsteps fields [v_0 .. v_{n-1}] an implementation reports for its own steps (a step is then judged on the field it actually sampled: on a
+    rough field the last bits of v_k move the samples of step k + 1 by more than that step's own rounding) -- while the interpolation of a
+    step and the chain rule g_k = g_{k+1} + gsrc_k + gflow_k run in float64.  Returns (out, gvec, per-step outputs): out = v_{n-1} +
+    warp_arbiter(v_{n-1}, v_{n-1}); per-step outputs [v_k + warp_arbiter(v_k, v_k) for every k] (what field k + 1 should be)."""
+    scale = 1.0 / (2 ** nsteps)
+    if fields is None:
+        v = torch.from_numpy(np.asarray(vec, dtype=np.float32)) * scale
+        fields = []
+        for _ in range(nsteps):
+            fields.append(v.numpy())
+            v = v + spatial_transformer(v, v)
+    assert len(fields) == nsteps
+    outs = [np.asarray(f, dtype=np.float64) + warp_arbiter(f, f)[0] for f in fields]
+    if gout is None:
+        return outs[-1], None, outs
+    g = np.asarray(gout, dtype=np.float64)
+    for f in reversed(fields):
+        _, gs, gf = warp_arbiter(f, f, g)
+        g = g + gs + gf
+    return outs[-1], g * scale, outs
+
+
 def resize_explicit(x, vel_resize):
     """Separable-lerp restatement of layers.py:85-97 / ATen upsample_trilinear3d
     (align_corners=True): out = floor(in*factor); src = dst*(in-1)/(out-1)."""

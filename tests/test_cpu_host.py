@@ -702,3 +702,122 @@ def test_pack_job_list_covers_the_whole_range_adjoint_of_unfused_upsampled_layer
     # levels by op 6 (conv, pool x 3), the collapsed upsample operators by the first cat([upsample, skip]) layer on the split engine)
     first = VF._prepack_plan(plan, params, 1, shape, True, False, dry=True)
     assert first[:2] == (2, 6) and first[2] > 6 and plan.ops[first[2]]["src"][1]
+
+
+# ------------------------------------------------------------------ the warp table (tests/warp_cases.py) and its float64 arbiter
+import warp_cases as wc                           # noqa: E402
+
+
+def _rel_l2(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def _fp32_reference(src, flow, gout):
+    s, f = torch.from_numpy(src).requires_grad_(), torch.from_numpy(flow).requires_grad_()
+    out = orc.spatial_transformer(s, f)
+    out.backward(torch.from_numpy(gout))
+    return out.detach().numpy(), s.grad.numpy(), f.grad.numpy()
+
+
+@pytest.mark.parametrize("case", wc.CASES, ids=wc.IDS)
+def test_warp_table_conditions_and_arbiter_vs_fp32_reference(case):
+    """A row cannot go vacuous: noise / rim / channels rows keep 10 - 60 % of their samples with an outside corner and at most 60 % of their
+    outputs exactly zero, a rim row a quarter to a half of its samples in (-1, 0) / (S - 1, S), the last-plane row samples exactly on 0 and
+    S - 1 and just beyond each, along every axis.  And the arbiter's `floor` is ATen's: the reference's fp32 out / gsrc / gflow agree with
+    oracle.warp_arbiter below 1e-6 on EVERY row -- the lattice rows included, where plain float64 grid_sample is 0.3 off in gflow."""
+    name, dims, B, C, recipe, _ = case
+    src, flow, gout = wc.arrays(case)
+    assert src.shape == (B, C) + dims and flow.shape == (B, len(dims)) + dims and np.prod(dims) <= 50000
+    coords = orc._src_coords_explicit(flow)
+    o64, gs64, gf64 = orc.warp_arbiter(src, flow, gout)
+    outside, rim = wc.corner_stats(coords, dims)
+    if recipe in wc.BANDED:
+        assert 0.10 <= outside <= 0.60, (name, outside)
+        assert float((o64 == 0).mean()) <= 0.60, name
+    if recipe == "rim":
+        assert 0.25 <= rim <= 0.50, (name, rim)
+    if recipe == "lattice":
+        for x in coords:       # on a lattice point (floor flips, one weight is 0) for a third of the samples, else on a half point; the fp32 round trip
+            assert float((x == np.round(x)).mean()) >= 0.3 and float(np.abs(2 * x - np.round(2 * x)).max()) < 1e-5, name      # leaves some one ulp beside
+    if recipe == "last_plane":
+        for a, S in enumerate(dims):
+            x = coords[a][a]                                       # sample a carries axis a
+            assert (x == S - 1).sum() >= 5 and (x == 0).sum() >= 5, (name, a)
+            assert ((x > S - 1) & (x < S - 1 + 1e-3)).sum() >= 5 and ((x < 0) & (x > -1e-3)).sum() >= 5, (name, a)
+            assert ((x < S - 1) & (x > S - 1 - 1e-4)).sum() >= 1, (name, a)
+    ro, rgs, rgf = _fp32_reference(src, flow, gout)
+    if recipe == "far":
+        assert sorted(map(str, np.unique(flow[~np.isfinite(flow) | (np.abs(flow) >= 1e4)]))) == sorted(map(str, np.float32(wc.FAR_VALUES)))
+        assert np.isfinite(ro).all() and np.isfinite(rgs).all() and np.isfinite(rgf).all()      # 3-D: a wild displacement samples 0, no gradient
+        assert np.isfinite(o64).all() and np.isfinite(gs64).all() and np.isfinite(gf64).all()
+        with np.errstate(invalid="ignore"):
+            wild = np.broadcast_to(np.any(np.abs(flow) >= 1e4, axis=1, keepdims=True), ro.shape)
+        assert np.all(ro[wild] == 0) and np.all(o64[wild] == 0)
+    assert _rel_l2(ro, o64) < 1e-6 and _rel_l2(rgs, gs64) < 1e-6 and _rel_l2(rgf, gf64) < 1e-6, name
+    if len(dims) == 3 and recipe != "far":
+        from oracle import c_oracle
+        assert _rel_l2(c_oracle.warp3d(src, flow), o64) < 1e-6, name
+
+
+@pytest.mark.parametrize("row", wc.FUSED, ids=wc.FUSED_IDS)
+def test_warp_fused_rows_and_vecint_rows(row):
+    """Fused rows: F.interpolate onto the image's extents is oracle.resize_transform(x, 0.5) where the image is twice the field; the upsampled
+    field keeps 10 - 60 % of its samples with an outside corner; the reference agrees with the arbiter below 1e-6.  VecInt rows (checked with
+    the first fused row only): 10 - 40 % of the first step's samples at the rim, fp32 reference vs vecint_arbiter below 1e-6."""
+    name, low, full, _ = row
+    img, fl, gout = wc.fused_arrays(row)
+    pos = torch.nn.functional.interpolate(2.0 * torch.from_numpy(fl), size=full, mode="trilinear", align_corners=True)
+    if full == tuple(2 * s for s in low):
+        assert torch.equal(pos, orc.resize_transform(torch.from_numpy(fl), 0.5))
+    pos = pos.numpy()
+    outside, _ = wc.corner_stats(orc._src_coords_explicit(pos), full)
+    assert 0.10 <= outside <= 0.60, (name, outside)
+    ro, _, rgf = _fp32_reference(img, pos, gout)
+    o64, _, gf64 = orc.warp_arbiter(img, pos, gout)
+    assert _rel_l2(ro, o64) < 1e-6 and _rel_l2(rgf, gf64) < 1e-6
+    if row is not wc.FUSED[0]:
+        return
+    for dims, _ in wc.VECINT:
+        for nsteps in wc.VECINT_STEPS:
+            vec, g = wc.vecint_arrays(dims, nsteps)
+            _, rim = wc.corner_stats(orc._src_coords_explicit(vec * np.float32(2.0 ** -nsteps)), dims)
+            assert 0.10 <= rim <= 0.40, (dims, nsteps, rim)
+            v = torch.from_numpy(vec).requires_grad_()
+            out = orc.vecint(v, nsteps)
+            out.backward(torch.from_numpy(g))
+            o64, g64, _ = orc.vecint_arbiter(vec, nsteps, g)
+            assert _rel_l2(out.detach().numpy(), o64) < 1e-6 and _rel_l2(v.grad.numpy(), g64) < 1e-6, (dims, nsteps)
+
+
+@pytest.mark.parametrize("kind", wc.FOOTPRINT)
+def test_warp_footprint_inputs_are_not_vacuous(kind):
+    """The inputs of test_gpu_warp.py::test_warp_non_finite_footprint, on the CPU: the reference's non-finite set is non-empty and below 5 % of
+    the voxels; at least 5 samples have an outside corner whose CLAMPED index names a poisoned voxel while the reference is finite there (the
+    samples clamped-load-times-zero arithmetic would poison); and the arbiter, which skips outside corners, has the reference's set except
+    where ATen's 2-D sampler makes NaN of a non-finite COORDINATE (VecInt 2-D: the two poisoned voxels themselves)."""
+    dims = wc.FOOTPRINT_DIMS[kind]
+    x, fl, gout, where = wc.footprint_arrays(kind)
+    xp = wc.poisoned(x, where)
+    if kind.startswith("vecint"):
+        ref = orc.vecint(torch.from_numpy(xp), 1).numpy()
+        flow = xp * np.float32(0.5)
+        arb = flow.astype(np.float64) + orc.warp_arbiter(flow, flow)[0]
+    else:
+        flow = fl if kind != "fused" else torch.nn.functional.interpolate(2.0 * torch.from_numpy(fl), size=dims, mode="trilinear", align_corners=True).numpy()
+        ref = orc.spatial_transformer(torch.from_numpy(xp), torch.from_numpy(flow)).numpy()
+        arb = orc.warp_arbiter(xp, flow)[0]
+    nonfinite = ~np.isfinite(ref)
+    mask = (~np.isfinite(xp)).any(axis=1)
+    hits = wc.clamped_poison_hits(orc._src_coords_explicit(flow), dims, mask) & ~nonfinite.any(axis=1)
+    assert 0 < nonfinite.sum() < 0.05 * ref.size and hits.sum() >= 5, (kind, int(nonfinite.sum()), int(hits.sum()))
+    differ = nonfinite != ~np.isfinite(arb)
+    if kind == "vecint2d":
+        assert differ.sum() == 2 and np.all(np.broadcast_to(mask[:, None], differ.shape)[differ])
+    else:
+        assert not differ.any()
+    if kind in ("warp3d", "warp2d"):                              # the backward half: a NaN in gout at the centre voxel reaches corners inside the volume
+        gn = gout.copy()
+        gn[(0, 0) + tuple(d // 2 for d in dims)] = np.nan
+        _, rgs, rgf = _fp32_reference(x, flow, gn)
+        assert 0 < (~np.isfinite(rgs)).sum() <= 2 ** len(dims) and 0 < (~np.isfinite(rgf)).sum() <= len(dims)

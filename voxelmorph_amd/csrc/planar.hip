@@ -46,6 +46,15 @@ __device__ __forceinline__ Corners4 corners4(float y, float x, int H, int W) {
     return c;
 }
 
+template <unsigned FUSED>
+__device__ __forceinline__ float corner_sum4(const float (&v)[4], const float (&w)[4]) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = ((FUSED >> k) & 1u) ? __builtin_fmaf(v[k], w[k], acc) : acc + v[k] * w[k];
+    return acc;
+}
+
 template <int MODE>
 __global__ void __launch_bounds__(256) k_warp2d_fwd(const float* __restrict__ src, const float* __restrict__ flow, float* __restrict__ out,
                                                     int C, int H, int W) {
@@ -62,12 +71,17 @@ __global__ void __launch_bounds__(256) k_warp2d_fwd(const float* __restrict__ sr
         return;
     }
     const Corners4 cn = corners4(y, x, H, W);
+    // grid_sampler_2d forms 0 * w for an outside corner: a non-finite coordinate (NaN weights) gives NaN, not the 0 of the 3-D sampler
+    const bool bad = !(fabsf(y) < __builtin_inff()) || !(fabsf(x) < __builtin_inff());
     for (int c = 0; c < C; ++c) {
         const float* sc = s + (size_t)c * V;
-        float acc = 0.0f;
+        float v[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc += sc[cn.idx[k]] * cn.w[k];
-        o[(size_t)c * V] = acc;
+        for (int k = 0; k < 4; ++k) v[k] = cn.ok[k] ? sc[cn.idx[k]] : 0.0f;       // an outside corner is not loaded (Inf * 0 = NaN)
+        // roundings pinned to what the kernel has always computed (see corner_sum8 in warp.hip): channels were taken in pairs with every product
+        // fused, an odd last channel on its own with only the last one fused
+        const float acc = c < (C & ~1) ? corner_sum4<0xFu>(v, cn.w) : corner_sum4<0x9u>(v, cn.w);
+        o[(size_t)c * V] = bad ? __builtin_nanf("") : acc;
     }
 }
 
@@ -117,15 +131,17 @@ __global__ void __launch_bounds__(256) k_vecint2d_step_fwd(const float* __restri
     VXM_PIXEL_INDEX(H, W);
     const float* vin = in + (size_t)b * 2 * V;
     const float v0 = vin[p] * scale, v1 = vin[V + p] * scale;
-    const Corners4 cn = corners4(vxm_src_coord(h, v0, H), vxm_src_coord(w, v1, W), H, W);
+    const float y = vxm_src_coord(h, v0, H), x = vxm_src_coord(w, v1, W);
+    const Corners4 cn = corners4(y, x, H, W);
+    const bool bad = !(fabsf(y) < __builtin_inff()) || !(fabsf(x) < __builtin_inff());       // as k_warp2d_fwd: NaN, in both channels
     float a0 = 0.0f, a1 = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        a0 += (vin[cn.idx[k]] * scale) * cn.w[k];
-        a1 += (vin[V + cn.idx[k]] * scale) * cn.w[k];
+        a0 += ((cn.ok[k] ? vin[cn.idx[k]] : 0.0f) * scale) * cn.w[k];                 // an outside corner is not loaded (Inf * 0 = NaN)
+        a1 += ((cn.ok[k] ? vin[V + cn.idx[k]] : 0.0f) * scale) * cn.w[k];
     }
     float* o = out + (size_t)b * 2 * V + p;
-    o[0] = v0 + a0; o[V] = v1 + a1;
+    o[0] = bad ? __builtin_nanf("") : v0 + a0; o[V] = bad ? __builtin_nanf("") : v1 + a1;
 }
 
 // backward of one step (see k_vecint_step_bwd in warp.hip for the derivation); gin zeroed by the caller, fp32 atomics

@@ -46,8 +46,9 @@ __device__ __forceinline__ float vxm_src_coord(int i, float f, int S) {
 
 // One axis of ATen's grid_sampler_3d corner construction: x0 = floor(x), weights (x0 + 1 - x) and (x - x0).
 // The two corner indices are clamped into the volume (so that every gather address is valid) and the in-volume
-// tests kept separately: padding_mode='zeros' is applied by zeroing the WEIGHT (forward) or the VALUE (backward)
-// of an outside corner, which leaves the in-volume terms bit-identical and needs no branches.
+// tests kept separately: padding_mode='zeros' is applied by zeroing the VALUE of an outside corner -- the forward does not
+// load it at all (an out-of-range buffer offset / a select: a weight of zero alone turns an Inf or NaN in the clamped voxel
+// into NaN, which ATen's zero padding never reads) -- which leaves the in-volume terms bit-identical and needs no branches.
 struct AxisTaps { int i0, i1; float w0, w1; bool ok0, ok1; };
 __device__ __forceinline__ AxisTaps axis_corners(float x, int S) {
     AxisTaps a;

@@ -16,6 +16,7 @@ namespace {
 // the 8 corners in ATen's order k = 4 dz + 2 dy + dx: plane offsets, trilinear weights (wz wy) wx, validity
 struct Corners8 {
     int idx[8];
+    int off4[8];              // byte offset of the corner for a buffer load; VXM_OOB for a corner outside the volume: the load returns 0.0
     float w[8];
     bool ok[8];
     float wz[2], wy[2], wx[2];
@@ -23,7 +24,12 @@ struct Corners8 {
 __device__ __forceinline__ Corners8 corners8(float z, float y, float x, int D, int H, int W) {
     const AxisTaps az = axis_corners(z, D), ay = axis_corners(y, H), ax = axis_corners(x, W);
     Corners8 c;
-    c.wz[0] = az.w0; c.wz[1] = az.w1; c.wy[0] = ay.w0; c.wy[1] = ay.w1; c.wx[0] = ax.w0; c.wx[1] = ax.w1;
+    // a non-finite coordinate (Inf - Inf, NaN weights) has no corner in the volume and, in grid_sampler_3d_backward, no gradient on ANY axis: its
+    // weights are zeroed, or the backward's 0 * w of the other two axes would be NaN
+    const float inf = __builtin_inff();
+    const bool fz = fabsf(z) < inf, fy = fabsf(y) < inf, fx = fabsf(x) < inf;
+    c.wz[0] = fz ? az.w0 : 0.0f; c.wz[1] = fz ? az.w1 : 0.0f; c.wy[0] = fy ? ay.w0 : 0.0f; c.wy[1] = fy ? ay.w1 : 0.0f;
+    c.wx[0] = fx ? ax.w0 : 0.0f; c.wx[1] = fx ? ax.w1 : 0.0f;
     const int iz[2] = {az.i0, az.i1}, iy[2] = {ay.i0, ay.i1}, ix[2] = {ax.i0, ax.i1};
     const bool oz[2] = {az.ok0, az.ok1}, oy[2] = {ay.ok0, ay.ok1}, ox[2] = {ax.ok0, ax.ok1};
 #pragma unroll
@@ -38,10 +44,25 @@ __device__ __forceinline__ Corners8 corners8(float z, float y, float x, int D, i
                 const int k = 4 * dz + 2 * dy + dx;
                 c.idx[k] = row + ix[dx];
                 c.ok[k] = ozy && ox[dx];
+                c.off4[k] = c.ok[k] ? c.idx[k] << 2 : VXM_OOB;
                 c.w[k] = c.ok[k] ? wzy * c.wx[dx] : 0.0f;
             }
         }
     return c;
+}
+
+// The corner sum sum_k v[k] w[k], k ascending, with its roundings PINNED: bit k of FUSED set -> acc = fma(v[k], w[k], acc) (one rounding), clear ->
+// acc = acc + round(v[k] w[k]).  Left to -ffp-contract=fast the choice per corner is the compiler's and moves with unrelated edits (a select
+// next to a load changed it); the masks below are the ones the kernels have always computed with, so their results keep their bits.
+constexpr unsigned WARP_FUSED = 0xE7u;                        // k_warp3d_fwd, k_warp3d_up_fwd, channel 0 of k_vecint_step_fwd: corners 3 and 4 unfused
+constexpr unsigned VECINT_FUSED12 = 0xC3u;                    // channels 1 and 2 of k_vecint_step_fwd: corners 2 - 5 unfused
+template <unsigned FUSED>
+__device__ __forceinline__ float corner_sum8(const float (&v)[8], const float (&w)[8]) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc = ((FUSED >> k) & 1u) ? __builtin_fmaf(v[k], w[k], acc) : acc + v[k] * w[k];
+    return acc;
 }
 
 // Thread -> voxel without a per-voxel div/mod chain: grid = (ceil(H W / 256), D, B); one division by W per thread.
@@ -82,11 +103,8 @@ __global__ void __launch_bounds__(256) k_warp3d_fwd(const float* __restrict__ sr
         const __amdgpu_buffer_rsrc_t rs = vxm_rsrc(s + (size_t)c * V, (unsigned)V4), ro = vxm_rsrc(o + (size_t)c * V, (unsigned)V4);
         float v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = vxm_bload(rs, cn.idx[k] << 2, 0);       // 8 independent gathers in flight
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc += v[k] * cn.w[k];
-        vxm_bstore(acc, ro, p4, 0);
+        for (int k = 0; k < 8; ++k) v[k] = vxm_bload(rs, cn.off4[k], 0);           // 8 independent gathers in flight; an outside corner loads 0.0
+        vxm_bstore(corner_sum8<WARP_FUSED>(v, cn.w), ro, p4, 0);
     }
 }
 
@@ -151,17 +169,11 @@ __global__ void __launch_bounds__(256) k_vecint_step_fwd(const float* __restrict
     const Corners8 cn = corners8(vxm_src_coord(d, v0, D), vxm_src_coord(h, v1, H), vxm_src_coord(w, v2, W), D, H, W);
     float s0[8], s1[8], s2[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {                                     // 24 independent gathers in flight
-        const int i4 = cn.idx[k] << 2;
-        s0[k] = vxm_bload(ri, i4, 0); s1[k] = vxm_bload(ri, i4, V4); s2[k] = vxm_bload(ri, i4, 2 * V4);
+    for (int k = 0; k < 8; ++k) {                                     // 24 independent gathers in flight; an outside corner loads 0.0
+        const int i4 = cn.off4[k];
+        s0[k] = vxm_bload(ri, i4, 0) * scale; s1[k] = vxm_bload(ri, i4, V4) * scale; s2[k] = vxm_bload(ri, i4, 2 * V4) * scale;
     }
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        a0 += (s0[k] * scale) * cn.w[k];
-        a1 += (s1[k] * scale) * cn.w[k];
-        a2 += (s2[k] * scale) * cn.w[k];
-    }
+    const float a0 = corner_sum8<WARP_FUSED>(s0, cn.w), a1 = corner_sum8<VECINT_FUSED12>(s1, cn.w), a2 = corner_sum8<VECINT_FUSED12>(s2, cn.w);
     vxm_bstore(v0 + a0, ro, p4, 0); vxm_bstore(v1 + a1, ro, p4, V4); vxm_bstore(v2 + a2, ro, p4, 2 * V4);
 }
 
@@ -968,11 +980,8 @@ __global__ void __launch_bounds__(256) k_warp3d_up_fwd(const float* __restrict__
             const __amdgpu_buffer_rsrc_t rs = vxm_rsrc(s + (size_t)c * V, (unsigned)V4), ro = vxm_rsrc(o + (size_t)c * V, (unsigned)V4);
             float v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = vxm_bload(rs, cn.idx[k] << 2, 0);
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc += v[k] * cn.w[k];
-            vxm_bstore(acc, ro, p4, 0);
+            for (int k = 0; k < 8; ++k) v[k] = vxm_bload(rs, cn.off4[k], 0);
+            vxm_bstore(corner_sum8<WARP_FUSED>(v, cn.w), ro, p4, 0);
         }
     }
 }
