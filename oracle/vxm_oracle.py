@@ -616,10 +616,17 @@ def _box_axis_explicit(x, ax, w, p, adjoint=False):
     O = S + 2 * p - w + 1
     if O <= 0:
         raise ValueError("window %d larger than the padded axis (%d + 2*%d)" % (w, S, p))
+    # w shifted slices, not a difference of running sums: a NaN / Inf entry reaches exactly the sums whose window holds it (a running
+    # sum would carry it to the end of the axis), and no cancellation of a long prefix
     pad = [(0, 0)] * x.ndim
-    pad[ax] = (p + 1, p)
-    cs = np.cumsum(np.pad(x, pad), axis=ax)
-    return np.take(cs, np.arange(w, w + O), axis=ax) - np.take(cs, np.arange(0, O), axis=ax)
+    pad[ax] = (p, p)
+    xp = np.pad(x, pad)
+    out = None
+    for k in range(w):
+        sl = [slice(None)] * x.ndim
+        sl[ax] = slice(k, k + O)
+        out = xp[tuple(sl)].copy() if out is None else out + xp[tuple(sl)]
+    return out
 
 
 def ncc_explicit_win(I, J, win, grad=False):

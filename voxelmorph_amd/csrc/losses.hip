@@ -444,7 +444,9 @@ __global__ void __launch_bounds__(256) k_gradloss_fwd(const float* __restrict__ 
 
 // W % 4 == 0: 16-byte loads, VXM_GRAD_RU consecutive rows per wave with all of their loads issued before the arithmetic (the
 // scalar kernel above keeps 4 dword loads per lane in flight: 1.07 TB/s on the 82 MB full-resolution field of the dense
-// configuration).  A neighbour that does not exist is replaced by the voxel itself -- its difference is 0 and pen(0) = 0.
+// configuration).  The load of a neighbour that does not exist is clamped onto the voxel itself and its difference is SELECTED to 0, which
+// drops the term as the scalar kernel and the reference do (pen(0) = 0; the clamped difference itself is 0 for a finite voxel, but
+// Inf - Inf = NaN for an infinite one).  The select sits on the difference, not on pen(): t * t still contracts into the running sum.
 #define VXM_GRAD_RU 4
 template <int L2>
 __global__ void __launch_bounds__(256) k_gradloss_fwd_v4(const float* __restrict__ y, double* __restrict__ acc, int C, int D, int H, int W) {
@@ -458,15 +460,18 @@ __global__ void __launch_bounds__(256) k_gradloss_fwd_v4(const float* __restrict
         for (int w4 = lane; w4 < W4; w4 += 64) {
             f32x4 v[VXM_GRAD_RU], vd[VXM_GRAD_RU], vh[VXM_GRAD_RU];
             float nx[VXM_GRAD_RU];
+            bool dn[VXM_GRAD_RU], hn[VXM_GRAD_RU];               // wave-uniform
+            const bool wn = w4 * 4 + 4 < W;                      // the last lane of a row has no right neighbour for its fourth voxel
 #pragma unroll
             for (int u = 0; u < VXM_GRAD_RU; ++u) {
                 const int r = min(r0 + u, nrow - 1);
                 const int h = r % H, d = (r / H) % D;
                 const float* row = yb + (size_t)r * W + w4 * 4;
+                dn[u] = d + 1 < D; hn[u] = h + 1 < H;
                 v[u] = *reinterpret_cast<const f32x4*>(row);
-                vd[u] = *reinterpret_cast<const f32x4*>(row + (d + 1 < D ? HW : 0));
-                vh[u] = *reinterpret_cast<const f32x4*>(row + (h + 1 < H ? W : 0));
-                nx[u] = row[w4 * 4 + 4 < W ? 4 : 3];
+                vd[u] = *reinterpret_cast<const f32x4*>(row + (dn[u] ? HW : 0));
+                vh[u] = *reinterpret_cast<const f32x4*>(row + (hn[u] ? W : 0));
+                nx[u] = row[wn ? 4 : 3];
             }
             float fd = 0.0f, fh = 0.0f, fw = 0.0f;
 #pragma unroll
@@ -474,9 +479,9 @@ __global__ void __launch_bounds__(256) k_gradloss_fwd_v4(const float* __restrict
                 if (r0 + u >= nrow) break;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    fd += pen<L2>(vd[u][k] - v[u][k]);
-                    fh += pen<L2>(vh[u][k] - v[u][k]);
-                    fw += pen<L2>((k < 3 ? v[u][k < 3 ? k + 1 : 3] : nx[u]) - v[u][k]);
+                    fd += pen<L2>(dn[u] ? vd[u][k] - v[u][k] : 0.0f);
+                    fh += pen<L2>(hn[u] ? vh[u][k] - v[u][k] : 0.0f);
+                    fw += pen<L2>((k < 3 || wn) ? (k < 3 ? v[u][k < 3 ? k + 1 : 3] : nx[u]) - v[u][k] : 0.0f);
                 }
             }
             sd += (double)fd; sh += (double)fh; sw += (double)fw;
@@ -531,7 +536,9 @@ __global__ void __launch_bounds__(256) k_gradloss_bwd(const float* __restrict__ 
     }
 }
 
-// W % 4 == 0: two rows per wave, seven loads per row issued together; absent neighbours are replaced by the voxel (dpen(0) = 0)
+// W % 4 == 0: two rows per wave, seven loads per row issued together; the load of an absent neighbour is clamped onto the voxel and its
+// difference selected to 0 (dpen(0) = 0 drops the term; voxel - voxel is NaN for an infinite voxel, where the scalar kernel and the
+// reference give +-Inf)
 template <int L2>
 __global__ void __launch_bounds__(256) k_gradloss_bwd_v4(const float* __restrict__ y, const float* __restrict__ gloss, float* __restrict__ gy,
                                                          int B, int C, int D, int H, int W, float mult, int axes) {
@@ -546,18 +553,21 @@ __global__ void __launch_bounds__(256) k_gradloss_bwd_v4(const float* __restrict
         for (int w4 = lane; w4 < W4; w4 += 64) {
             f32x4 v[2], dm[2], dq[2], hm[2], hq[2];
             float lf[2], rt[2];
+            bool dp[2], dn[2], hp[2], hn[2];                     // wave-uniform
+            const bool wp = w4 > 0, wn = w4 * 4 + 4 < W;         // the first / last lane of a row: no left / right neighbour beyond its four voxels
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int r = min(r0 + u, nrow - 1);
                 const int h = r % H, d = (r / H) % D;
                 const float* row = yb + (size_t)r * W + w4 * 4;
+                dp[u] = d > 0; dn[u] = d + 1 < D; hp[u] = h > 0; hn[u] = h + 1 < H;
                 v[u] = *reinterpret_cast<const f32x4*>(row);
-                dm[u] = *reinterpret_cast<const f32x4*>(row - (d > 0 ? HW : 0));
-                dq[u] = *reinterpret_cast<const f32x4*>(row + (d + 1 < D ? HW : 0));
-                hm[u] = *reinterpret_cast<const f32x4*>(row - (h > 0 ? W : 0));
-                hq[u] = *reinterpret_cast<const f32x4*>(row + (h + 1 < H ? W : 0));
-                lf[u] = row[w4 > 0 ? -1 : 0];
-                rt[u] = row[w4 * 4 + 4 < W ? 4 : 3];
+                dm[u] = *reinterpret_cast<const f32x4*>(row - (dp[u] ? HW : 0));
+                dq[u] = *reinterpret_cast<const f32x4*>(row + (dn[u] ? HW : 0));
+                hm[u] = *reinterpret_cast<const f32x4*>(row - (hp[u] ? W : 0));
+                hq[u] = *reinterpret_cast<const f32x4*>(row + (hn[u] ? W : 0));
+                lf[u] = row[wp ? -1 : 0];
+                rt[u] = row[wn ? 4 : 3];
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -567,8 +577,13 @@ __global__ void __launch_bounds__(256) k_gradloss_bwd_v4(const float* __restrict
                 for (int k = 0; k < 4; ++k) {
                     const float c = v[u][k];
                     const float wl = k > 0 ? v[u][k > 0 ? k - 1 : 0] : lf[u], wr = k < 3 ? v[u][k < 3 ? k + 1 : 3] : rt[u];
-                    g[k] = kd * (dpen<L2>(c - dm[u][k]) - dpen<L2>(dq[u][k] - c)) + kh * (dpen<L2>(c - hm[u][k]) - dpen<L2>(hq[u][k] - c))
-                           + kw * (dpen<L2>(c - wl) - dpen<L2>(wr - c));
+                    const float tdm = dp[u] ? c - dm[u][k] : 0.0f, tdq = dn[u] ? dq[u][k] - c : 0.0f;
+                    const float thm = hp[u] ? c - hm[u][k] : 0.0f, thq = hn[u] ? hq[u][k] - c : 0.0f;
+                    const float twl = (k > 0 || wp) ? c - wl : 0.0f, twr = (k < 3 || wn) ? wr - c : 0.0f;
+                    // the contraction is spelled out: left to the compiler it depends on how the selects above are scheduled, and the
+                    // rounding of a finite gradient must not (kw * w + (kd * d + (kh * h)), one rounding per product-sum)
+                    g[k] = __builtin_fmaf(kw, dpen<L2>(twl) - dpen<L2>(twr),
+                                          __builtin_fmaf(kd, dpen<L2>(tdm) - dpen<L2>(tdq), kh * (dpen<L2>(thm) - dpen<L2>(thq))));
                 }
                 *reinterpret_cast<f32x4*>(gb + (size_t)(r0 + u) * W + w4 * 4) = g;
             }
@@ -906,10 +921,19 @@ int vxm_ncc_win_bwd(const float* I, const float* J, const float* sums, const flo
     return vxm_check_launch("vxm_ncc_win_bwd");
 }
 
+// The reference takes the mean of no differences on an axis of one voxel and returns NaN; the kernels refuse the shape (and a batch
+// beyond gridDim.y), naming it.
+static int gradloss_shape(const char* fn, int B, int C, int D, int H, int W, int axes) {
+    const bool ok = B > 0 && B <= 65535 && C > 0 && (axes == 2 || D > 1) && H > 1 && W > 1;
+    if (axes == 2) VXM_REQUIRE(ok, VXM_ERR_BAD_SHAPE, "%s: bad shape [%d,%d,%d,%d] (every axis needs two voxels, B <= 65535)", fn, B, C, H, W);
+    VXM_REQUIRE(ok, VXM_ERR_BAD_SHAPE, "%s: bad shape [%d,%d,%d,%d,%d] (every axis needs two voxels, B <= 65535)", fn, B, C, D, H, W);
+    return VXM_OK;
+}
+
 static int gradloss_fwd(const char* fn, const float* y, float* loss, double* acc, int B, int C, int D, int H, int W, int penalty, float mult,
                         int axes, void* stream) {
     VXM_REQUIRE(y && loss && acc, VXM_ERR_NULL_POINTER, "%s: null pointer", fn);
-    VXM_REQUIRE(B > 0 && B <= 65535 && C > 0 && (axes == 2 || D > 1) && H > 1 && W > 1, VXM_ERR_BAD_SHAPE, "%s: bad shape", fn);
+    if (int e = gradloss_shape(fn, B, C, D, H, W, axes)) return e;
     VXM_REQUIRE(penalty == VXM_PENALTY_L1 || penalty == VXM_PENALTY_L2, VXM_ERR_UNSUPPORTED, "penalty can only be l1 or l2. Got: %d", penalty);
     hipStream_t s = VXM_STREAM(stream);
     (void)hipMemsetAsync(acc, 0, sizeof(double) * 3 * B * VXM_GRAD_SLOTS, s);
@@ -929,7 +953,7 @@ static int gradloss_fwd(const char* fn, const float* y, float* loss, double* acc
 static int gradloss_bwd(const char* fn, const float* y, const float* gloss, float* gy, int B, int C, int D, int H, int W, int penalty, float mult,
                         int axes, void* stream) {
     VXM_REQUIRE(y && gloss && gy, VXM_ERR_NULL_POINTER, "%s: null pointer", fn);
-    VXM_REQUIRE(B > 0 && B <= 65535 && C > 0 && (axes == 2 || D > 1) && H > 1 && W > 1, VXM_ERR_BAD_SHAPE, "%s: bad shape", fn);
+    if (int e = gradloss_shape(fn, B, C, D, H, W, axes)) return e;
     VXM_REQUIRE(penalty == VXM_PENALTY_L1 || penalty == VXM_PENALTY_L2, VXM_ERR_UNSUPPORTED, "penalty can only be l1 or l2. Got: %d", penalty);
     const long long rows4 = ((long long)C * D * H + 3) / 4;
     const dim3 grid((unsigned)(rows4 > 16384 ? 16384 : rows4), B);        // 4 rows per block and pass
