@@ -40,7 +40,7 @@ typedef enum {
 enum { VXM_INTERP_LINEAR = 0, VXM_INTERP_NEAREST = 1 };   /* SpatialTransformer mode, layers.py:11 */
 enum { VXM_PENALTY_L1 = 0, VXM_PENALTY_L2 = 1 };          /* Grad penalty, losses.py:98 */
 
-int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 502 = 0.5.2 (round 6; every 0.4 / 0.5.x entry point kept) */
+int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 503 = 0.5.3 (round 6; every 0.4 / 0.5.x entry point kept) */
 const char* vxm_last_error_string(void);
 
 /* ---- the two umbrella names SURVEY.md section 8b lists.  Every op has its own *_workspace_bytes() query next to it; this one dispatches
@@ -568,6 +568,37 @@ int vxm_conv3d_k3_s3u_bwd_weight_ok(int C0, int Cout, int B, int D, int H, int W
 size_t vxm_conv3d_k3_s3u_bwd_weight_workspace_bytes(int C0, int Cout, int B, int D, int H, int W);
 int vxm_conv3d_k3_s3u_bwd_weight(const float* x0, int C0, int64_t x0_bstride, const float* dz, int64_t dz_bstride, int Cout, float* gw,
                                  int gw_cin, void* work, size_t work_bytes, int B, int D, int H, int W, int pieces, void* stream);
+
+/* ---- evaluation metrics (csrc/metrics.hip): what a registration is scored by.  Stateless; the calls clear their own result buffers on the
+ * stream (a memset node when captured), allocate nothing and never synchronise; shapes and pointers are validated before any HIP call.
+ *
+ * vxm_label_overlap: the integer counts behind the hard Dice of voxelmorph/py/utils.py:265-287 for ALL labels in one pass over the two
+ * label maps (the reference makes three passes per label: :283-284).  a, b: fp32 label maps [B][N]; labels_sorted: L strictly increasing
+ * fp32 values in DEVICE memory, 1 <= L <= VXM_LABELS_MAX (else VXM_ERR_UNSUPPORTED); counts: int64 [B][L][3] =
+ * {|a == l and b == l|, |a == l|, |b == l|}.  `==` as numpy's `array == label`: a voxel whose value is not in the list (a non-integer, NaN,
+ * +-Inf) counts nowhere, -0.0 counts as 0.  Integer sums through integer atomics: bit-reproducible.  Dice = 2 counts[0] / max(counts[1] +
+ * counts[2], eps) is formed by the caller (voxelmorph_amd/metrics.py does it in float64 on the host, as :283-286 does).
+ * vxm_label_overlap_blocks: the number of blocks per batch item that call launches for N voxels (tests: where the second grid-stride pass begins). */
+#define VXM_LABELS_MAX 1024
+int vxm_label_overlap(const float* a, const float* b, const float* labels_sorted, int L, int64_t* counts, int B, int64_t N, void* stream);
+int vxm_label_overlap_blocks(int64_t N);
+/* The evaluation protocol of scripts/tf/test.py:109-112 in one launch: seg [B,1,D,H,W] is nearest-sampled at p + flow[b,:,p] (the coordinate
+ * arithmetic of vxm_warp3d_fwd(mode = VXM_INTERP_NEAREST), zeros outside) and each sampled label is counted against fixed [B,1,D,H,W] as
+ * above; the warped map is written only when warped != NULL.  counts (and warped) are bit-identical to vxm_warp3d_fwd followed by
+ * vxm_label_overlap. */
+int vxm_warp3d_label_overlap(const float* seg, const float* flow, const float* fixed, float* warped, const float* labels_sorted, int L,
+                             int64_t* counts, int B, int D, int H, int W, void* stream);
+/* jacobian_determinant, py/utils.py:473-516: det [B,D,H,W] (nullable) = det(I + grad disp) of disp [B,3,D,H,W] ([B,2,H,W] -> [B,H,W] in 2-D),
+ * channel a = the displacement along axis a in voxels (the model's layout), with np.gradient's differences (:496: central inside, one-sided
+ * on the first and last plane of an axis) and the cofactor expansion of :505-509 (3-D) / :516 (2-D).  The unit is added after the difference
+ * (the reference differentiates disp + grid; in fp32 that loses the low bits of disp to the grid coordinate).  stats (nullable): int64 [B][2] =
+ * {number of det <= 0 (folded voxels), number of non-finite det}.  Every extent >= 2 (VXM_ERR_BAD_SHAPE otherwise: np.gradient refuses such
+ * shapes too).  A NaN / Inf displacement makes exactly the voxels whose stencil reads it non-finite. */
+int vxm_jacdet3d(const float* disp, float* det, int64_t* stats, int B, int D, int H, int W, void* stream);
+int vxm_jacdet2d(const float* disp, float* det, int64_t* stats, int B, int H, int W, void* stream);
+/* planes of the first axis one block of vxm_jacdet3d marches over for this volume (tests: which shapes march, which end on a partial chunk); 0 for a
+ * shape it rejects */
+int vxm_jacdet3d_planes(int D, int H, int W);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,12 @@ SIGNATURES = {
     "vxm_add2": [_P, _P, _P, _L, _P],
     "vxm_adam_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P],
     "vxm_adam_step_dev": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _F, _P],
+    "vxm_label_overlap": [_P, _P, _P, _I, _P, _I, _L, _P],
+    "vxm_label_overlap_blocks": [_L],
+    "vxm_warp3d_label_overlap": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
+    "vxm_jacdet3d": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "vxm_jacdet2d": [_P, _P, _P, _I, _I, _I, _P],
+    "vxm_jacdet3d_planes": [_I, _I, _I],
 }
 _RESTYPES = {
     "vxm_workspace_bytes": _S,

@@ -1,0 +1,27 @@
+"""The part of `voxelmorph/py/utils.py` that an evaluation needs, under the reference's path (`vxm.py.utils.*`): the file-list readers
+(:32-66), the volume readers / writers (:69-158, from voxelmorph_amd/data.py) and the two metrics (:265-287, :473-516), which run on the
+device (voxelmorph_amd/metrics.py)."""
+from ..data import load_volfile, save_volfile  # noqa: F401
+from ..metrics import dice, jacobian_determinant  # noqa: F401
+
+
+def read_file_list(filename, prefix=None, suffix=None):
+    """Reads a list of files from a line-separated text file (py/utils.py:32-48): blank lines dropped, names stripped."""
+    with open(filename, 'r') as file:
+        filelist = [line.strip() for line in file if line.strip()]
+    if prefix is not None:
+        filelist = [prefix + f for f in filelist]
+    if suffix is not None:
+        filelist = [f + suffix for f in filelist]
+    return filelist
+
+
+def read_pair_list(filename, delim=None, prefix=None, suffix=None):
+    """Reads a list of registration file pairs from a line-separated text file (py/utils.py:51-66); `delim` separates the names of a
+    line (default: any whitespace); prefix / suffix are added to every name."""
+    pairlist = [f.split(delim) for f in read_file_list(filename)]
+    if prefix is not None:
+        pairlist = [[prefix + f for f in pair] for pair in pairlist]
+    if suffix is not None:
+        pairlist = [[f + suffix for f in pair] for pair in pairlist]
+    return pairlist
