@@ -537,10 +537,10 @@ def test_channel_blocked_tensor_rule(monkeypatch):
     assert VF._blocked_tensors(plan, 1, shape) == frozenset({rem0, rem1})
     monkeypatch.setattr(VF, "BLOCKED_LAST", True)
     few["bw"] = False                                    # the flow conv's weight gradient would not take a blocked x: the tensor stays planar
-    plan.__dict__.pop("_blocked_cache", None)
+    plan.__dict__.pop("_route_cache", None)
     assert VF._blocked_tensors(plan, 1, shape) == frozenset({rem0, rem1})
     few["bw"] = True
-    plan.__dict__.pop("_blocked_cache", None)
+    plan.__dict__.pop("_route_cache", None)
     monkeypatch.setattr(VF, "BLOCKED", False)
     assert VF._blocked_tensors(plan, 1, shape) == frozenset()
     monkeypatch.setattr(VF, "BLOCKED", True)
@@ -702,6 +702,54 @@ def test_pack_job_list_covers_the_whole_range_adjoint_of_unfused_upsampled_layer
     # levels by op 6 (conv, pool x 3), the collapsed upsample operators by the first cat([upsample, skip]) layer on the split engine)
     first = VF._prepack_plan(plan, params, 1, shape, True, False, dry=True)
     assert first[:2] == (2, 6) and first[2] > 6 and plan.ops[first[2]]["src"][1]
+
+
+def test_route_table_of_the_default_plan_names_the_kernel_families_of_every_conv():
+    """Host logic, no device: `functional._route_plan` is the one place that decides which kernel family each product of each conv op of
+    the fused U-Net runs on.  For the default VxmDense at 160x192x224, B = 1, default switches, the families below were read off the launches
+    of the code BEFORE the table existed (entry point per conv op of a recorded training step): op -> (forward, backward-data onto the
+    low-resolution producer, weight gradient).  The planners are views of the same table: `_s3_jobs` and `_prepack_plan(dry=True)` agree."""
+    import voxelmorph_amd as vxm
+    from voxelmorph_amd.torch import functional as VF
+    assert (VF.FP32_ENGINE, VF.S3U, VF.S3_UP, VF.SPLIT_48, VF.FEWCH_H) == ("f16x2", True, False, True, True)
+    shape = (160, 192, 224)
+    m = vxm.networks.VxmDense(shape, int_steps=7, int_downsize=2)
+    plan = m.unet_model.plan(m._feats, extra=((m.flow.out_channels, 1.0),))
+    params = m.unet_model.conv_params() + [m.flow.weight, m.flow.bias]
+    table = VF._route_plan(plan, 1, shape)
+    expected = {
+        0: ("fp32", None, "fewch"),              # 2 -> 16, 160x192x224 (few input channels: fp32 MFMA k-packed forward)
+        2: ("s3", None, "s3"),                   # 16 -> 32, 80x96x112
+        4: ("s3", None, "s3"),                   # 32 -> 32, 40x48x56
+        6: ("fp32", None, "fp32"),               # 32 -> 32, 20x24x28
+        8: ("fp32", None, "fp32"),               # 32 -> 32, 10x12x14
+        9: ("fp32", None, "fp32"),               # cat([up(32), 32]) -> 32, 20x24x28: too few tiles for every collapsed kernel
+        10: ("s3", None, "up+s3"),               # ... 40x48x56: split kernel through the upsampling gather, adjoint of the whole concat (round 5)
+        11: ("s3u", "s3u_dlow", "up+s3"),        # ... 80x96x112
+        12: ("s3u", "s3u_dlow", "s3u+s3"),       # cat([up(32), 16]) -> 32, 160x192x224
+        13: ("s3", None, "s3"),                  # 32 -> 16
+        14: ("s3", None, "s3"),                  # 16 -> 16
+        15: ("fewout", None, "fewch"),           # 16 -> 3, the flow conv
+    }
+    assert {n: (rt.fwd, rt.low, rt.bww) for n, rt in table.convs.items()} == expected
+    assert [(rt.c0, rt.c1, rt.cout) for rt in table.convs.values()] == [
+        (1, 1, 16), (16, 0, 32), (32, 0, 32), (32, 0, 32), (32, 0, 32), (32, 32, 32), (32, 32, 32), (32, 32, 32), (32, 16, 32), (32, 0, 16), (16, 0, 16),
+        (16, 0, 3)]
+    # backward-data ranges: the whole concat where nothing takes the upsampled segment (ops 9, 10), the skip segment alone where k_s3u_dlow does
+    assert table.convs[9].bwd == [(0, 64, False)] and table.convs[10].bwd == [(0, 64, True)]
+    assert table.convs[11].bwd == [(32, 64, True)] and table.convs[12].bwd == [(32, 48, True)] and table.convs[15].bwd == [(0, 16, False)]
+    # the planners say what the table says
+    jobs = [(tuple(w.shape[:2]), lo, hi, flip, seg0) for w, lo, hi, flip, seg0 in VF._s3_jobs(plan, params, 1, shape, True, False)]
+    from_table = [(tuple(params[2 * rt.k].shape[:2]),) + args for rt in table.convs.values() for _, kind, args, _ in rt.packs(True, False) if kind == "s3"]
+    assert jobs == from_table and len(jobs) == 12
+    assert [j for j in jobs if not j[3]] == [(tuple(params[2 * rt.k].shape[:2]), 0, rt.cin, False, rt.c0) for rt in table.convs.values() if rt.fwd == "s3"]
+    fwd_of = lambda fam: [n for n, rt in table.convs.items() if rt.fwd == fam]
+    first = VF._prepack_plan(plan, params, 1, shape, True, False, dry=True)
+    assert first == (fwd_of("s3")[0], [n for n in fwd_of("fp32") if n > 0][0], fwd_of("s3u")[0]) == (2, 6, 11)
+    # built on demand, on the main stream: op 0's fp32 operator, the forward operator and the whole-concat adjoint of op 9
+    on_demand = [(n,) + e[1:3] for n, rt in table.convs.items() for e in rt.packs(True, False) if e[0] is None]
+    assert on_demand == [(0, "fp32", (False, 0, 2)), (9, "fp32", (False, 0, 64)), (9, "fp32", (True, 0, 64))]
+    assert sorted(table.blocked) == sorted(VF._blocked_tensors(plan, 1, shape)) == [14, 15, 16]
 
 
 # ------------------------------------------------------------------ the warp table (tests/warp_cases.py) and its float64 arbiter

@@ -2204,3 +2204,104 @@ def test_native_comm_two_ranks_agree(vxm, tmp_path):
     ok, refused = out.stdout.count("ranks ok"), out.stdout.count("fell back together")
     print(out.stdout.strip().splitlines()[-2:])
     assert (ok, refused) in ((2, 0), (0, 2)), out.stdout[-2000:]
+
+
+# ------------------------------------------------------------------ the route table against the launches of a step
+# entry point -> kernel family, as functional.conv_fwd_route / conv_bwd_low_route / conv_bwd_weight_route name them
+_FWD_FAMILY = {"vxm_conv3d_k3_fewout_fwd": "fewout", "vxm_conv3d_k3_fewout_fwd_layout": "fewout", "vxm_conv3d_k3_s3u_fwd": "s3u",
+               "vxm_conv3d_k3_s3u_fwd_signs": "s3u", "vxm_conv3d_k3_s3_fwd": "s3", "vxm_conv3d_k3_up_fwd": "up", "vxm_conv3d_k3_fwd": "fp32",
+               "vxm_conv3d_k3_fwd_layout": "fp32"}
+_BWD_FAMILY = dict(_FWD_FAMILY, **{"vxm_conv3d_k3_s3u_bwd_data": "s3u_pc", "vxm_conv3d_k3_s3u_bwd_low": "s3u_dlow", "vxm_conv3d_k3_up_bwd_low": "dlow",
+                                   "vxm_conv3d_k3_s3_bwd_weight": "w:s3", "vxm_conv3d_k3_s3u_bwd_weight": "w:s3u", "vxm_conv3d_k3_fewch_bwd_weight": "w:fewch",
+                                   "vxm_conv3d_k3_fewch_bwd_weight_pool": "w:fewch", "vxm_conv3d_k3_bwd_weight_up_segment": "w:up",
+                                   "vxm_conv3d_k3_bwd_weight": "w:fp32"})
+_BWW_LAUNCHES = {"s3": ["w:s3"], "s3u+s3": ["w:s3u", "w:s3"], "fewch": ["w:fewch"], "up+s3": ["w:up", "w:s3"], "fp32": ["w:fp32"]}
+# `*pack_weights*` calls of one step outside _prepack_plan at 32x32x32, B = 1, on the code before the route table existed (its launch trace,
+# profiles/pr07_launch_trace.txt: the pack launches of step 2 on the main stream), by (thresholds forced to one tile, VXM_S3U)
+_ON_DEMAND_PACKS_BEFORE = {(True, True): 1, (True, False): 2, (False, True): 9}
+
+
+def test_route_table_names_the_launches_of_a_step(vxm):
+    """functional._route_plan against what a training step of VxmDense (32x32x32, B = 1) really launches, in the environment the test runs in.
+    (a) For every conv op the entry points called in the forward, the backward-data (onto the low-resolution producer, and per channel range)
+    and the weight gradient are the ones the table names, in launch order.  (b) With every parameter's version bumped, the packed operators
+    built OUTSIDE _prepack_plan -- on demand, on the main stream, in the middle of the chain -- are exactly the ones the table marks so, and
+    no more than before the table existed.  (Round 5 found such a pack with a profiler: 0.23 ms per step.)"""
+    import importlib.util
+    from voxelmorph_amd.torch import functional as VF
+    spec = importlib.util.spec_from_file_location("launch_trace", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "launch_trace.py"))
+    lt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lt)
+    shape = (32, 32, 32)
+    torch.manual_seed(0)
+    model = vxm.networks.VxmDense(shape, int_steps=7, int_downsize=2).cuda()
+    src, trg = torch.rand((1, 1) + shape, device="cuda"), torch.rand((1, 1) + shape, device="cuda")
+    inside, prepack = [], VF._prepack_plan
+
+    def marked_prepack(*a, **k):
+        begin = len(rec.calls)
+        try:
+            return prepack(*a, **k)
+        finally:
+            inside.extend(range(begin, len(rec.calls)))
+
+    def step():
+        y, pre = model(src, trg)
+        mid = len(rec.calls)
+        (vxm.losses.NCC().loss(trg, y) + 0.01 * vxm.losses.Grad("l2", loss_mult=2).loss(None, pre)).backward()
+        torch.cuda.synchronize()
+        return mid
+
+    VF._prepack_plan = marked_prepack
+    try:
+        with lt.Recorder(VF) as rec:
+            step()
+            with torch.no_grad():
+                for p in model.parameters():
+                    p.add_(0)
+            model.zero_grad()
+            begin = len(rec.calls)
+            mid = step()
+    finally:
+        VF._prepack_plan = prepack
+    plan = model.unet_model.plan(model._feats, extra=((model.flow.out_channels, 1.0),))
+    table = VF._route_plan(plan, 1, shape)
+    convs = list(table.convs.values())
+    names = [name for name, _ in rec.calls]
+    # (a) forward: one launch per conv op, in op order
+    got = [_FWD_FAMILY[n] for n in names[begin:mid] if n in _FWD_FAMILY]
+    print("[route] forward  ", got)
+    assert got == [rt.fwd for rt in convs]
+    # ... backward: per conv op from the last to the first, the weight gradient's launches, then (unless it feeds the network inputs, which ask
+    # for no gradient) the low-resolution product and one launch per channel range
+    want = []
+    for rt in reversed(convs):
+        want += _BWW_LAUNCHES[rt.bww]
+        if not rt.feeds_inputs:
+            want += ([rt.low] if rt.low is not None else []) + ["s3" if split else "fp32" for _, _, split in rt.bwd]
+    got = [_BWD_FAMILY[n] for n in names[mid:] if n in _BWD_FAMILY]
+    print("[route] backward ", got)
+    assert got == want
+    # (b) packs on demand
+    got = sorted((n, a[2:7] if n.endswith("_range") else a[2:5]) for i, (n, a) in enumerate(rec.calls) if i >= begin and "pack_weights" in n and i not in inside)
+    want = sorted(("vxm_conv3d_k3_pack_weights_range", (rt.cin, rt.cout, args[1], args[2] - args[1], int(args[0]))) if kind == "fp32" else
+                  ("vxm_conv3d_k3_up_pack_weights", (rt.c0, rt.c1, rt.cout))
+                  for rt in convs for grp, kind, args, _ in rt.packs(True, False) if grp is None)
+    print("[route] on demand", got)
+    assert got == want
+    assert len(got) <= _ON_DEMAND_PACKS_BEFORE[(bool(os.environ.get("VXM_S3_MIN_TILES")), VF.S3U)]
+
+
+def test_route_table_on_every_split_family_in_subprocess():
+    """the check above with the tile thresholds of the split kernels forced to one, where a 32x32x32 volume reaches every split family (the
+    [32, 16] adjoint pair of the 48-channel layer included), and with VXM_S3U=0: the gather-through-upsampling forward and the adjoint of the
+    whole concat"""
+    if os.environ.get("VXM_S3_MIN_TILES"):
+        pytest.skip("already inside the forced run")
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for env in ({"VXM_S3_MIN_TILES": "1", "VXM_S3U_MIN_TILES": "1", "VXM_S3U_BWW_MIN_TILES": "1"}, {"VXM_S3_MIN_TILES": "1", "VXM_S3U": "0"}):
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"), "-k",
+                            "route_table_names_the_launches"], env=dict(os.environ, **env), cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]

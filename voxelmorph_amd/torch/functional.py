@@ -7,6 +7,7 @@ calls into libvxm_hip.so on the current HIP stream.  PyTorch is used for device 
 import ctypes
 import math
 import os
+from functools import cached_property
 
 import torch
 
@@ -53,7 +54,6 @@ BLOCKED_LAST = os.environ.get("VXM_BLOCKED_LAST", "1") != "0"
 # the main chain on one queue and every weight gradient on a second one, as launch-by-launch submission does: 7.0 ms of overlap and 0.05 ms
 # idle per step instead of 3.7 and 0.14), "before" otherwise (launch by launch: 83.4 / 81.6 against 82.0 / 81.2).  VXM_DW_ORDER=before|after forces one.
 DW_ORDER = os.environ.get("VXM_DW_ORDER", "")
-BW_REDUCE_STREAM = os.environ.get("VXM_BW_REDUCE_STREAM", "") == "1"     # UnetFn.backward: weight-gradient reductions on a third stream (A/B: slower)
 # few-channel weight gradients (first block, flow conv) on the fp16 pieces (csrc/conv_bwd_weight.hip k_fewch_bwd_weight_h); VXM_FEWCH_H=0: fp32 MFMA
 FEWCH_H = os.environ.get("VXM_FEWCH_H", "1") != "0"
 # the first block's weight gradient forms the gradient at its pre-activation on the fly from the operands of the pooling backward (16-bit codes from
@@ -78,8 +78,8 @@ def fp32_engine_note():
             "v_mfma_f32_16x16x4_f32")
 
 
-def _side_stream(dev, which=0):
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), which)
+def _side_stream(dev):
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return _SIDE_STREAMS[key]
@@ -492,22 +492,11 @@ def pack_weights_cached(w, flip, lo=0, hi=None):
     """pack_weights with the packed operator cached on the weight tensor until its version moves (as the split operators): the fused U-Net
     builds the ones it will ask for on the second stream at the start of a step (_prepack_plan) instead of one small launch in front of
     every fp32-MFMA conv of the main chain"""
-    cin = w.shape[1]
+    cout, cin = w.shape[:2]
     hi = cin if hi is None else hi
-    cache = w.__dict__.setdefault("_vxm_s3_packs", {})
-    key = ("fp32", bool(flip), lo, hi)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == _pack_ver(w) and hit[1].device == w.device:
-        return hit[1]
-    cout = w.shape[0]
-    n = _lib.lib().vxm_conv3d_k3_packed_elems(cout if flip else hi - lo, hi - lo if flip else cout)
-    wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == n else None
-    if wp is None:
-        wp = torch.empty(n, dtype=w.dtype, device=w.device)
-        _FRESH_PACKS.append(wp)
-    call("vxm_conv3d_k3_pack_weights_range", ptr(_c(w)), ptr(wp), cin, cout, lo, hi - lo, 1 if flip else 0, stream())
-    cache[key] = (_pack_ver(w), wp)
-    return wp
+    return _cached_pack(w, ("fp32", bool(flip), lo, hi), lambda: _lib.lib().vxm_conv3d_k3_packed_elems(cout if flip else hi - lo, hi - lo if flip else cout),
+                        lambda wp: call("vxm_conv3d_k3_pack_weights_range", ptr(_c(w)), ptr(wp), cin, cout, lo, hi - lo, 1 if flip else 0, stream()),
+                        dtype=w.dtype)
 
 
 def _pack_ver(t):
@@ -544,10 +533,25 @@ def _probe(tag, t, C, blocked):
 _FRESH_PACKS = []      # pack buffers allocated since the last _adopt_fresh_packs(): allocated under the second stream, read on the main one
 
 
-def _new_pack(nbytes, device):
-    t = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    _FRESH_PACKS.append(t)
-    return t
+def _cached_pack(w, key, count, build, dtype=torch.uint8):
+    """The packed operator `key` of weight tensor w, cached on w until its version moves (once per optimiser step).  A stale one is rebuilt
+    by build(buffer) -- in the buffer it had when count(), its size in elements of `dtype` (bytes for the split operators), and w's device
+    still fit; a new buffer is registered in _FRESH_PACKS.  build=None (s3_prepack, which builds all its stale operators in one launch):
+    returns (buffer, commit), commit being None for a current operator and otherwise the call that marks it built."""
+    cache = w.__dict__.setdefault("_vxm_s3_packs", {})
+    hit = cache.get(key)
+    if hit is not None and hit[0] == _pack_ver(w) and hit[1].device == w.device:
+        return hit[1] if build is not None else (hit[1], None)
+    n, ver = int(count()), _pack_ver(w)
+    wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == n else None
+    if wp is None:
+        wp = torch.empty(n, dtype=dtype, device=w.device)
+        _FRESH_PACKS.append(wp)
+    if build is None:
+        return wp, lambda: cache.__setitem__(key, (ver, wp))
+    build(wp)
+    cache[key] = (ver, wp)
+    return wp
 
 
 def _adopt_fresh_packs(stream_):
@@ -561,29 +565,23 @@ def _adopt_fresh_packs(stream_):
 def s3_prepack(jobs):
     """Pack every stale split operator of `jobs` = [(w, lo, hi, flip, seg0), ...] in ONE launch (vxm_conv3d_k3_s3_pack_weights_batch).
     The packed, pre-split copies are cached on the weight tensor until its version moves (once per optimiser step)."""
-    import ctypes
-    stale = []
+    stale = {}         # (weight tensor, key) -> (pack job, commit)
     for w, lo, hi, flip, seg0 in jobs:
-        cache = w.__dict__.setdefault("_vxm_s3_packs", {})
         key = (lo, hi, bool(flip), seg0, s3_pieces())
-        hit = cache.get(key)
-        if hit is not None and hit[0] == _pack_ver(w) and hit[1].device == w.device:
-            continue
-        if any(k is cache and kk == key for (_, _, _, _, _, _, _, _, k, kk, _) in stale):
+        if (id(w), key) in stale:
             continue
         cout, cin = w.shape[:2]
         inc, outc = (cout, hi - lo) if flip else (hi - lo, cout)
-        nbytes = _lib.lib().vxm_conv3d_k3_s3_packed_bytes(seg0, inc - seg0, outc, s3_pieces())
-        wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == nbytes else _new_pack(nbytes, w.device)
-        stale.append((_c(w), cin, cout, lo, hi - lo, bool(flip), seg0, wp, cache, key, _pack_ver(w)))
+        wp, commit = _cached_pack(w, key, lambda: _lib.lib().vxm_conv3d_k3_s3_packed_bytes(seg0, inc - seg0, outc, s3_pieces()), None)
+        if commit is not None:
+            wc = _c(w)
+            stale[(id(w), key)] = (_lib.S3PackJob(wc.data_ptr(), wp.data_ptr(), cin, cout, lo, hi - lo, 1 if flip else 0, seg0, s3_pieces()), commit, wc)
     if not stale:
         return
-    table = (_lib.S3PackJob * len(stale))()
-    for j, (w, cin, cout, lo, n, flip, seg0, wp, _, _, _) in enumerate(stale):
-        table[j] = _lib.S3PackJob(w.data_ptr(), wp.data_ptr(), cin, cout, lo, n, 1 if flip else 0, seg0, s3_pieces())
+    table = (_lib.S3PackJob * len(stale))(*[job for job, _, _ in stale.values()])
     call("vxm_conv3d_k3_s3_pack_weights_batch", ctypes.cast(table, ctypes.c_void_p), len(stale), stream())
-    for _, _, _, _, _, _, _, wp, cache, key, ver in stale:
-        cache[key] = (ver, wp)
+    for _, commit, _ in stale.values():
+        commit()
 
 
 def s3_pack(w, flip, lo, hi, seg0):
@@ -599,17 +597,9 @@ def s3u_route(c0, c1, cout, B, D, H, W):
 def s3u_pack(w, c0, c1):
     """packed operator of the split + collapsed forward kernel (collapsed 2x2x2 weights per output parity class for the upsampled
     segment, the 27 taps for the skip segment, pre-split), cached on the weight tensor until its version moves"""
-    cache = w.__dict__.setdefault("_vxm_s3_packs", {})
-    key = ("s3u", c0, c1, s3_pieces())
-    hit = cache.get(key)
-    if hit is not None and hit[0] == _pack_ver(w) and hit[1].device == w.device:
-        return hit[1]
     cout = w.shape[0]
-    nbytes = _lib.lib().vxm_conv3d_k3_s3u_packed_bytes(c0, c1, cout, s3_pieces())
-    wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == nbytes else _new_pack(nbytes, w.device)
-    call("vxm_conv3d_k3_s3u_pack_weights", ptr(_c(w)), ptr(wp), c0, c1, cout, s3_pieces(), stream())
-    cache[key] = (_pack_ver(w), wp)
-    return wp
+    return _cached_pack(w, ("s3u", c0, c1, s3_pieces()), lambda: _lib.lib().vxm_conv3d_k3_s3u_packed_bytes(c0, c1, cout, s3_pieces()),
+                        lambda wp: call("vxm_conv3d_k3_s3u_pack_weights", ptr(_c(w)), ptr(wp), c0, c1, cout, s3_pieces(), stream()))
 
 
 def s3u_launch(x0, c0, bs0, x1, c1, bs1, wp, bias, y, ybs, cout, slope, B, D, H, W, lay=0, signs=None):
@@ -635,15 +625,8 @@ def s3u_bwd_low_pack(w, c0, cin):
     """packed transposed-collapsed operator of k_s3u_dlow for the first c0 input channels of w [cout][cin][27], cached on the weight tensor until
     its version moves"""
     cout = w.shape[0]
-    cache = w.__dict__.setdefault("_vxm_s3_packs", {})
-    key = ("s3u_low", c0, cin, s3_pieces())
-    hit = cache.get(key)
-    if hit is None or hit[0] != _pack_ver(w) or hit[1].device != w.device:
-        nbytes = _lib.lib().vxm_conv3d_k3_s3u_bwd_low_packed_bytes(c0, cout, s3_pieces())
-        wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == nbytes else _new_pack(nbytes, w.device)
-        call("vxm_conv3d_k3_s3u_bwd_low_pack_weights", ptr(_c(w)), ptr(wp), c0, cin, cout, s3_pieces(), stream())
-        cache[key] = hit = (_pack_ver(w), wp)
-    return hit[1]
+    return _cached_pack(w, ("s3u_low", c0, cin, s3_pieces()), lambda: _lib.lib().vxm_conv3d_k3_s3u_bwd_low_packed_bytes(c0, cout, s3_pieces()),
+                        lambda wp: call("vxm_conv3d_k3_s3u_bwd_low_pack_weights", ptr(_c(w)), ptr(wp), c0, cin, cout, s3_pieces(), stream()))
 
 
 def s3u_bwd_low(dz, cout, w, c0, cin, gxl, mask, mask_slope, B, D, H, W, lay=0):
@@ -665,15 +648,8 @@ def s3u_bwd_skip_pack(w, c0, c1):
     """packed adjoint operator of the skip channels [c0, c0 + c1) of w [cout][c0 + c1][27] for k_s3u_bwd_pc, cached on the weight tensor until its
     version moves"""
     cout = w.shape[0]
-    cache = w.__dict__.setdefault("_vxm_s3_packs", {})
-    key = ("s3u_skip_adj", c0, c1, s3_pieces())
-    hit = cache.get(key)
-    if hit is None or hit[0] != _pack_ver(w) or hit[1].device != w.device:
-        nbytes = _lib.lib().vxm_conv3d_k3_s3u_bwd_skip_packed_bytes(c1, cout, s3_pieces())
-        wp = hit[1] if hit is not None and hit[1].device == w.device and hit[1].numel() == nbytes else _new_pack(nbytes, w.device)
-        call("vxm_conv3d_k3_s3u_bwd_skip_pack_weights", ptr(_c(w)), ptr(wp), c0, c1, cout, s3_pieces(), stream())
-        cache[key] = hit = (_pack_ver(w), wp)
-    return hit[1]
+    return _cached_pack(w, ("s3u_skip_adj", c0, c1, s3_pieces()), lambda: _lib.lib().vxm_conv3d_k3_s3u_bwd_skip_packed_bytes(c1, cout, s3_pieces()),
+                        lambda wp: call("vxm_conv3d_k3_s3u_bwd_skip_pack_weights", ptr(_c(w)), ptr(wp), c0, c1, cout, s3_pieces(), stream()))
 
 
 def s3u_bwd_data(dz, cout, w, c0, c1, gxl, mask, mask_slope, gx1, B, D, H, W, lay=0):
@@ -746,11 +722,71 @@ def _need_split_kernel(lay, what):
                            "tensors whose producer and consumers run on them" % (what, lay))
 
 
+# --------------------------------------------------------------------------- routes: which kernel family one conv product runs on
+# Pure host functions of the shape (c0, up0, c1, cout, B, D, H, W) of ONE conv over the virtual tensor cat([x0 or upsample(x0), x1]) (c1 == 0: no
+# second segment) and of the module switches.  They launch and allocate nothing.  conv_forward / conv_bwd_data / conv_bwd_weight dispatch on
+# them with the addresses of their operands; the planners of the fused U-Net (_route_plan) read them per op with a stand-in aligned address,
+# which every tensor the engine allocates has.  The leaves (s3_route, s3u_route, ...) are the C side's shape tests behind the switches.
+_ALIGNED = 256           # stand-in for the address of a tensor the engine allocates itself (the *_ok predicates look at 16-byte alignment only)
+
+
+def conv_fwd_route(c0, up0, c1, cout, B, D, H, W, lay=0, at=None):
+    """family of a conv forward: "fewout" (at most 4 output channels, vector ALU), "s3u" (split + collapsed), "s3" (split), "up" (collapsed
+    fp32 MFMA) or "fp32" (plain fp32 MFMA).  at: (x0, batch stride, x1, batch stride, y, batch stride) of the launch; lay: its layout flags."""
+    V = D * H * W
+    x0, bs0, x1, bs1, y, ybs = at if at is not None else (_ALIGNED, c0 * (V // 8 if up0 else V), _ALIGNED if c1 else None, c1 * V, _ALIGNED, cout * V)
+    if (lay & ~S3_IN0_BLOCKED) == 0 and cout <= 4 and c1 == 0 and not up0 and _lib.lib().vxm_conv3d_k3_fewout_ok(x0, bs0, y, ybs, c0, cout, W):
+        return "fewout"
+    if up0 and s3u_route(c0, c1, cout, B, D, H, W):
+        return "s3u"
+    if s3_route(c0, up0, c1, cout, B, D, H, W):
+        return "s3"
+    if up0 and _lib.lib().vxm_conv3d_k3_up_ok(x0, c0, bs0, x1, c1, bs1, y, cout, B, D, H, W):
+        return "up"
+    return "fp32"
+
+
+def conv_bwd_data_routes(cin, cout, B, D, H, W):
+    """the launches of a backward-data onto `cin` input channels (dz has cout): [(lo, hi, split kernel?)] over the channel ranges of _bwd_bounds"""
+    bounds = _bwd_bounds(cin)
+    return [(lo, hi, bool(s3_route(cout, False, 0, hi - lo, B, D, H, W))) for lo, hi in zip(bounds[:-1], bounds[1:])]
+
+
+def conv_bwd_low_route(c0, c1, cout, B, D, H, W):
+    """family of the backward-data of an upsampled segment straight onto its low-resolution producer: "s3u_pc" (k_s3u_bwd_pc: the skip segment's
+    gradient from the same staging of dz), "s3u_dlow" (k_s3u_dlow), "dlow" (fp32, k_conv3d_k3_dlow) or None (the adjoint of the whole virtual
+    concat at this level, then the upsampling backward).  dz is a tensor of the engine's own (or the contiguous gradient autograd hands it)."""
+    s3u = s3u_bwd_low_route(c0, cout, B, D, H, W)
+    if not (s3u or _lib.lib().vxm_conv3d_k3_up_bwd_low_ok(_ALIGNED, cout * D * H * W, c0, cout, B, D, H, W)):
+        return None
+    if c1 and s3u_bwd_data_route(c0, c1, cout, B, D, H, W):
+        return "s3u_pc"
+    return "s3u_dlow" if s3u else "dlow"
+
+
+def conv_bwd_weight_route(c0, up0, c1, cout, B, D, H, W, at=None):
+    """family of a weight gradient: "s3" (split), "s3u+s3" (upsampled segment split + collapsed, skip segment split), "fewch" (few-channel kernel on
+    the fp16 pieces), "up+s3" (upsampled segment collapsed fp32 MFMA, skip segment split) or "fp32".  at: (x0, batch stride, x1, batch stride, dz)."""
+    L, V = _lib.lib(), D * H * W
+    x0, bs0, x1, bs1, dz = at if at is not None else (_ALIGNED, c0 * (V // 8 if up0 else V), _ALIGNED if c1 else None, c1 * V, _ALIGNED)
+    if split_engine() and not up0 and c1 == 0 and L.vxm_conv3d_k3_s3_bwd_weight_ok(c0, cout, B, D, H, W):
+        return "s3"
+    if up0 and c1 and s3u_bwd_weight_route(c0, cout, B, D, H, W) and L.vxm_conv3d_k3_s3_bwd_weight_ok(c1, cout, B, D, H, W):
+        return "s3u+s3"
+    if FEWCH_H and split_engine() and s3_pieces() == 2 and not up0 and L.vxm_conv3d_k3_fewch_bwd_weight_ok(x0, c0, bs0, x1, c1, bs1, dz, cout * V, cout, 2, W):
+        return "fewch"
+    if split_engine() and up0 and c1 and L.vxm_conv3d_k3_s3_bwd_weight_ok(c1, cout, B, D, H, W) and \
+            L.vxm_conv3d_k3_bwd_weight_variant(x0, c0, bs0, 1, x1, c1, bs1, dz, cout * V, cout, D, H, W) // 10 == 2:
+        return "up+s3"
+    return "fp32"
+
+
 def conv_forward(x0, c0, bs0, up0, x1, c1, bs1, w, bias, y, ybs, cout, slope, B, D, H, W, lay=0, signs=None):
     """ConvBlock / flow conv forward (networks.py:299-305, 211,257) from the reference-layout weights: the MFMA implicit
     GEMM (weights packed per call), or the vector-ALU kernel when there are at most 4 output channels (flow conv).
     lay: S3_IN0_BLOCKED (x0) / S3_OUT_BLOCKED (y) for channel-blocked tensors between split kernels (fused U-Net only)."""
-    if (lay & ~S3_IN0_BLOCKED) == 0 and cout <= 4 and x1 is None and not up0 and _lib.lib().vxm_conv3d_k3_fewout_ok(ptr(x0), bs0, ptr(y), ybs, c0, cout, W):
+    route = conv_fwd_route(c0, up0, c1 if x1 is not None else 0, cout, B, D, H, W, lay=lay, at=(ptr(x0), bs0, ptr(x1), bs1, ptr(y), ybs))
+    if route == "fewout":
         with _prof.region("k_conv3d_k3_fewout<%d>" % cout, flops=2.0 * 27 * c0 * cout * B * D * H * W):
             if lay:      # x0 channel-blocked: the last activation of the fused U-Net (_blocked_tensors)
                 call("vxm_conv3d_k3_fewout_fwd_layout", ptr(x0), c0, bs0, ptr(_c(w)), ptr(bias), ptr(y), ybs, cout, float(slope), B, D, H, W, lay, stream())
@@ -759,18 +795,16 @@ def conv_forward(x0, c0, bs0, up0, x1, c1, bs1, w, bias, y, ybs, cout, slope, B,
         return
     if signs is not None and not (lay & S3_OUT_BLOCKED):
         raise RuntimeError("conv_forward: a sign tensor goes with a channel-blocked output")
-    if up0 and s3u_route(c0, c1, cout, B, D, H, W):
+    if route == "s3u":
         s3u_launch(x0, c0, bs0, x1, c1, bs1, s3u_pack(w, c0, c1), bias, y, ybs, cout, slope, B, D, H, W, lay=lay, signs=signs)
         return
-    if s3_route(c0, up0, c1, cout, B, D, H, W):
-        if signs is not None:        # (a forward launch has no mask: the sign tensor of its output travels in that argument, flag OUT_SIGNS)
-            s3_launch(x0, c0, bs0, up0, x1, c1, bs1, s3_pack(w, False, 0, c0 + c1, c0), bias, y, ybs, cout, slope, signs, (cout // 4) * D * H * W, 1.0,
-                      B, D, H, W, lay=lay | S3_OUT_SIGNS)
-        else:
-            s3_launch(x0, c0, bs0, up0, x1, c1, bs1, s3_pack(w, False, 0, c0 + c1, c0), bias, y, ybs, cout, slope, None, 0, 1.0, B, D, H, W, lay=lay)
+    if route == "s3":
+        # (a forward launch has no mask: the sign tensor of its output travels in that argument, flag OUT_SIGNS)
+        s3_launch(x0, c0, bs0, up0, x1, c1, bs1, s3_pack(w, False, 0, c0 + c1, c0), bias, y, ybs, cout, slope, signs,
+                  (cout // 4) * D * H * W if signs is not None else 0, 1.0, B, D, H, W, lay=lay | (S3_OUT_SIGNS if signs is not None else 0))
         return
     _need_split_kernel(lay, "conv_forward")
-    if up0 and _lib.lib().vxm_conv3d_k3_up_ok(ptr(x0), c0, bs0, ptr(x1), c1, bs1, ptr(y), cout, B, D, H, W):
+    if route == "up":
         # upsampled segment at low-resolution cost: collapsed 2x2x2 weights per output parity (conv_fwd.hip: k_conv3d_k3_t8u)
         wp = torch.empty(_lib.lib().vxm_conv3d_k3_up_packed_elems(c0, c1, cout), dtype=w.dtype, device=w.device)
         call("vxm_conv3d_k3_up_pack_weights", ptr(_c(w)), ptr(wp), c0, c1, cout, stream())
@@ -788,17 +822,13 @@ def conv_bwd_data(dz, cout, w, gx, cin, mask, mask_slope, B, D, H, W, w_lo=0, la
     A 48-channel result (16 mod 32) is produced as 32 + 16 channels: two launches of the 8-wave kernel's 2- and
     1-tile instances beat one launch of the 3-tile instance (which only exists in the 4-wave kernel)."""
     V = D * H * W
-    bounds = _bwd_bounds(cin)
-    for lo, hi in zip(bounds[:-1], bounds[1:]):         # w_lo: gx covers the input channels [w_lo, w_lo + cin) of w
-        if s3_route(cout, False, 0, hi - lo, B, D, H, W):
+    for lo, hi, split in conv_bwd_data_routes(cin, cout, B, D, H, W):      # w_lo: gx covers the input channels [w_lo, w_lo + cin) of w
+        if split:
             if lay & S3_OUT_BLOCKED and (lo, hi) != (0, cin):   # (S3_REVERSE_TILES needs no such care: every launch of the pair walks backwards)
                 raise RuntimeError("conv_bwd_data: a channel-blocked gradient is written by one launch")
-            if lay & S3_MASK_SIGNS:      # `mask` is the sign tensor [B][cin / 4][D][H][W] (bytes) of the activation; one launch (blocked output)
-                s3_launch(dz, cout, cout * V, False, None, 0, 0, s3_pack(w, True, w_lo + lo, w_lo + hi, cout), None, gx, cin * V, cin,
-                          1.0, mask, (cin // 4) * V, mask_slope, B, D, H, W, lay=lay)
-                continue
+            signs = lay & S3_MASK_SIGNS  # `mask` is the sign tensor [B][cin / 4][D][H][W] (bytes) of the activation; one launch (blocked output)
             s3_launch(dz, cout, cout * V, False, None, 0, 0, s3_pack(w, True, w_lo + lo, w_lo + hi, cout), None, gx[:, lo:hi], cin * V, hi - lo,
-                      1.0, mask[:, lo:hi] if mask is not None else None, cin * V, mask_slope, B, D, H, W, lay=lay)
+                      1.0, mask if signs or mask is None else mask[:, lo:hi], (cin // 4) * V if signs else cin * V, mask_slope, B, D, H, W, lay=lay)
             continue
         lay &= ~S3_REVERSE_TILES                         # a scheduling hint of the split kernels only
         if lay & S3_OUT_BLOCKED and not (lay & S3_IN0_BLOCKED) and (lo, hi) == (0, cin):
@@ -832,7 +862,7 @@ def _claim_sink(p):
 class _Workspace:
     """Grow-only scratch shared by the bwd-weight launches of one backward pass.  `deferred`: a list that collects the reductions of the
     split weight-gradient kernels instead of running them behind their contraction (each then keeps a buffer of its own until it has run:
-    UnetFn.backward sends them to a third stream, see VXM_S3_BW_CONTRACT_ONLY in include/vxm_hip.h)."""
+    the phase flags VXM_S3_BW_CONTRACT_ONLY / VXM_S3_BW_REDUCE_ONLY of include/vxm_hip.h; tests/test_gpu_s3.py runs the two phases apart)."""
 
     def __init__(self, device, deferred=None):
         self.buf = None
@@ -882,42 +912,35 @@ def s3u_bwd_weight(ws, x0, c0, bs0, dz, cout, gw, gw_cin, B, D, H, W, lay=0):
 
 def conv_bwd_weight(ws, x0, c0, bs0, up0, x1, c1, bs1, dz, cout, gw, gb, B, D, H, W, lay=0):
     """lay: S3_IN0_BLOCKED (x0 of a plain conv) / S3_IN1_BLOCKED (dz) for channel-blocked tensors between split kernels (fused U-Net only)"""
-    if split_engine() and not up0 and x1 is None and _lib.lib().vxm_conv3d_k3_s3_bwd_weight_ok(c0, cout, B, D, H, W):
+    route = conv_bwd_weight_route(c0, up0, c1 if x1 is not None else 0, cout, B, D, H, W, at=(ptr(x0), bs0, ptr(x1), bs1, ptr(dz)))
+    if route == "s3":
         s3_bwd_weight(ws, x0, c0, bs0, dz, cout, gw, c0, 0, gb, B, D, H, W, lay=lay)
         return
-    if up0 and x1 is not None and s3u_bwd_weight_route(c0, cout, B, D, H, W) and _lib.lib().vxm_conv3d_k3_s3_bwd_weight_ok(c1, cout, B, D, H, W):
+    if route == "s3u+s3":
         # cat([upsample(x0), x1]) on the split engine: the upsampled segment through the collapsed split kernel (conv_s3u.hip: k_s3u_bww), the
         # full-resolution skip segment (and the bias gradient) through k_s3_bwd_weight, each into its channel range of gw
         s3u_bwd_weight(ws, x0, c0, bs0, dz, cout, gw, c0 + c1, B, D, H, W, lay=lay & S3_IN1_BLOCKED)
         s3_bwd_weight(ws, x1, c1, bs1, dz, cout, gw, c0 + c1, c0, gb, B, D, H, W, lay=lay & S3_IN1_BLOCKED)
         return
-    if FEWCH_H and split_engine() and s3_pieces() == 2 and not up0 and _lib.lib().vxm_conv3d_k3_fewch_bwd_weight_ok(
-            ptr(x0), c0, bs0, ptr(x1), c1, bs1, ptr(dz), cout * D * H * W, cout, 2, W):
-        if lay & ~S3_IN0_BLOCKED or (lay and not (c0 == 16 and c1 == 0 and cout <= 3)):
-            _need_split_kernel(lay, "conv_bwd_weight")
+    if lay and not (route == "fewch" and lay == S3_IN0_BLOCKED and c0 == 16 and c1 == 0 and cout <= 3):
+        _need_split_kernel(lay, "conv_bwd_weight")
+    buf = ws.get(_lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(c0 + c1, cout, B, D, H, W))
+    if route == "fewch":
         # first block (2 -> 16) / flow conv (16 -> 3): the few-channel kernel on the fp16 pieces (round 6; the fp32-MFMA form spent 62 % of its
         # time with the matrix pipe busy, and the first block's launch is the last thing a step waits for)
-        need = _lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(c0 + c1, cout, B, D, H, W)
-        buf = ws.get(need)
         with _prof.region("k_fewch_bwd_weight_h", flops=2.0 * 27 * (c0 + c1) * cout * B * D * H * W):
             call("vxm_conv3d_k3_fewch_bwd_weight", ptr(x0), c0, bs0, ptr(x1), c1, bs1, ptr(dz), cout * D * H * W, cout, ptr(gw), ptr(gb), ptr(buf),
                  buf.numel(), B, D, H, W, 2 | lay, stream())
         return
-    _need_split_kernel(lay, "conv_bwd_weight")
-    if split_engine() and up0 and x1 is not None and _lib.lib().vxm_conv3d_k3_s3_bwd_weight_ok(c1, cout, B, D, H, W) and \
-            _lib.lib().vxm_conv3d_k3_bwd_weight_variant(ptr(x0), c0, bs0, 1, ptr(x1), c1, bs1, ptr(dz), cout * D * H * W, cout, D, H, W) // 10 == 2:
+    if route == "up+s3":
         # cat([upsample(x0), x1]): the upsampled segment through the collapsed fp32-MFMA kernel, the full-resolution skip segment (and the
         # bias gradient) on the split kernel, each into its channel range of gw
-        need = _lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(c0 + c1, cout, B, D, H, W)
-        buf = ws.get(need)
         with _prof.region("k_conv3d_k3_bwd_weight_up<%d>" % (1 if cout <= 16 else 2), flops=2.0 * 8 * c0 * cout * B * D * H * W,
                           nominal=2.0 * 27 * c0 * cout * B * D * H * W):
             call("vxm_conv3d_k3_bwd_weight_up_segment", ptr(x0), c0, bs0, ptr(x1), c1, bs1, ptr(dz), cout * D * H * W, cout, ptr(gw), ptr(buf),
                  buf.numel(), B, D, H, W, stream())
         s3_bwd_weight(ws, x1, c1, bs1, dz, cout, gw, c0 + c1, c0, gb, B, D, H, W)
         return
-    need = _lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(c0 + c1, cout, B, D, H, W)
-    buf = ws.get(need)
     name, nominal = None, 2.0 * 27 * (c0 + c1) * cout * B * D * H * W
     flops = nominal
     if _prof.ACTIVE is not None:
@@ -1134,165 +1157,187 @@ def _bwd_bounds(cin):
     return [0, cin]
 
 
+class _ConvRoute:
+    """What the fused U-Net decides about ONE conv op of a plan at one (B, volume): channels, extent and topology, and the kernel family of
+    each of its products (conv_*_route), each asked once, on first use.  Everything that plans or runs the op reads this record."""
+
+    def __init__(self, plan, n, B, shape3):
+        op = plan.ops[n]
+        s0, up0, s1 = op["src"]
+        self.n, self.k, self.dst, self.s0, self.up0, self.s1, self.slope = n, op["k"], op["dst"], s0, bool(up0), s1, op["slope"]
+        self.cout, self.c0, self.c1 = plan.ch[op["dst"]], plan.ch[s0], plan.ch[s1] if s1 is not None else 0
+        self.cin = self.c0 + self.c1
+        self.feeds_inputs = s0 < plan.n_inputs      # the first layer: (s0, s1) is the virtual concat of the one or two network inputs
+        self.lvl = plan.lvl[op["dst"]]
+        self.geom = (B, self.D, self.H, self.W) = (B,) + _dims(shape3, self.lvl)
+        # s0 is the output of a ConvBlock that nothing else reads: its LeakyReLU' is fused into the launch that produces its gradient
+        only_reader = not self.feeds_inputs and plan.ops[plan.producer[s0]]["kind"] == "conv" and len(plan.consumers[s0]) == 1
+        self.pslope = plan.ops[plan.producer[s0]]["slope"] if only_reader else None
+        self.up_fused = self.up0 and only_reader                     # ... into the backward-data onto the low-resolution tensor
+        self.fuse = not self.up0 and s1 is None and only_reader      # ... into the epilogue of the plain backward-data
+
+    fwd = cached_property(lambda self: conv_fwd_route(self.c0, self.up0, self.c1, self.cout, *self.geom))
+    bww = cached_property(lambda self: conv_bwd_weight_route(self.c0, self.up0, self.c1, self.cout, *self.geom))
+    low = cached_property(lambda self: conv_bwd_low_route(self.c0, self.c1, self.cout, *self.geom) if self.up_fused else None)
+
+    # the split engine takes the backward-data onto the low-resolution producer (k_s3u_dlow, or k_s3u_bwd_pc which contains it)
+    low_s3u = cached_property(lambda self: self.up_fused and bool(s3u_bwd_low_route(self.c0, self.cout, *self.geom)))
+    # launches (lo, hi, split?) of the adjoint onto the skip channels [c0, c0 + c1) of w alone
+    skip_bwd = cached_property(lambda self: [(self.c0 + lo, self.c0 + hi, sp) for lo, hi, sp in conv_bwd_data_routes(self.c1, self.cout, *self.geom)] if self.c1 else [])
+
+    @cached_property
+    def bwd(self):
+        """launches (lo, hi, split?) over the input channels of w that conv_bwd_data is asked for.  An upsampled segment goes straight onto
+        the low-resolution tensor when a kernel takes the shape (`low`: then only the skip segment needs an adjoint here, and k_s3u_bwd_pc
+        computes that too); otherwise the adjoint of the WHOLE virtual concat runs at this level.  (Round 5: that operator was missing from
+        the pack list, and was built on demand in the middle of the backward-data chain -- 0.23 ms behind the persistent blocks of the weight
+        gradients, every step, at the 40x48x56 level of the default U-Net.)"""
+        if self.up0 and self.low is not None:
+            return [] if self.low == "s3u_pc" else self.skip_bwd
+        return conv_bwd_data_routes(self.cin, self.cout, *self.geom)
+
+    def packs(self, with_backward, input_grads):
+        """The packed operators this op asks for, in the order they are built: (group, kind, args, read by the forward pass?).  Group "A": split
+        operators, args of an s3_prepack job behind w; "B1" / "B2": args of pack_weights_cached / s3u_pack / s3u_bwd_low_pack /
+        s3u_bwd_skip_pack behind w (_prepack_plan); None: built on demand on the main stream, in front of the launch that reads it."""
+        # the fp32-MFMA operators of the convs the split engine does not take (coarse levels): packed ahead too, so that the main chain does not
+        # carry a 5 us pack launch in front of each of them.  (op 0 needs its operator at once: on demand; as it was, so does a cat([upsample,
+        # skip]) layer that no collapsed kernel takes: the coarsest one of the default U-Net, 20x24x28.  The collapsed fp32 operator is not cached.)
+        out = {"s3": [("A", "s3", (0, self.cin, False, self.c0), True)], "s3u": [("B2", "s3u", (self.c0, self.c1), True)],
+               "up": [(None, "up", (self.c0, self.c1), True)], "fewout": [],
+               "fp32": [("B1" if self.n > 0 and not self.up0 else None, "fp32", (False, 0, self.cin), True)]}[self.fwd]
+        if not with_backward or (self.feeds_inputs and not input_grads):
+            return out
+        if self.low in ("s3u_pc", "s3u_dlow"):
+            out.append(("B2", "s3u_low", (self.c0, self.cin), False))
+            if self.low == "s3u_pc":
+                out.append(("B2", "s3u_skip", (self.c0, self.c1), False))
+        # fp32-MFMA adjoints are built ahead for the ranges a plain conv, or the skip segment of a cat([upsample, skip]) layer, hands to
+        # conv_bwd_data.  Where no kernel takes the upsampled segment onto the low-resolution tensor (`low` is None: the coarsest cat layer of
+        # the default U-Net, 20x24x28) the adjoint of the whole concat is still built on demand, and the skip segment's ahead, unused: kept as
+        # it was measured, and visible here.
+        ahead = [] if self.feeds_inputs else self.skip_bwd if self.up0 else self.bwd
+        for lo, hi, split in self.bwd:
+            out.append(("A", "s3", (lo, hi, True, self.cout), False) if split else
+                       ("B2" if (lo, hi, split) in ahead else None, "fp32", (True, lo, hi), False))
+        out += [("B2", "fp32", (True, lo, hi), False) for lo, hi, split in ahead if not split and (lo, hi, split) not in self.bwd]
+        return out
+
+
+class _RouteTable:
+    """_ConvRoute per conv op of a plan at one (B, volume) and set of switches, plus what follows from several of them at once"""
+
+    def __init__(self, plan, B, shape3):
+        self.plan = plan
+        self.convs = {n: _ConvRoute(plan, n, B, shape3) for n, op in enumerate(plan.ops) if op["kind"] == "conv"}
+
+    @cached_property
+    def blocked(self):
+        """Which activations of the fused U-Net are kept CHANNEL-BLOCKED ([B][C/8][D][H][W][8], include/vxm_hip.h VXM_S3_*_BLOCKED) instead of
+        NCDHW.  The tensors never leave the engine, so their layout is its own business; a haloed row of a blocked tensor is one contiguous run
+        and the split kernels, which are bound by the vector L1's sector requests, stage it 15 - 20 % faster.  A tensor t
+        qualifies when every kernel that writes or reads t, or the gradient DZ[t] (which takes the same layout), is a split kernel with a
+        blocked variant at this shape: t is the output of a ConvBlock, read by exactly one plain ConvBlock (forward, weight gradient, and the
+        fused backward-data that produces DZ[t] with t as its mask), and its producer's backward (weight gradient and backward-data, which read
+        DZ[t]) runs on the split kernels too.  In the default VxmDense U-Net: the outputs of remaining[0], remaining[1] and remaining[2]."""
+        plan, out, L = self.plan, set(), _lib.lib()
+        if not (BLOCKED and split_engine() and s3_pieces() == 2):
+            return frozenset()
+
+        def one_blocked(launches, lo, hi, cin, H):      # a forward-type product cin -> hi - lo channels: ONE launch of a split instance with a blocked variant?
+            return hi - lo > 4 and launches == [(lo, hi, True)] and bool(L.vxm_conv3d_k3_s3_layout_ok(cin, 0, 0, hi - lo, H, 2))
+
+        def plain(rt):                                  # forward, weight gradient and backward-data of a plain conv
+            return rt.s1 is None and not rt.up0 and one_blocked([(0, rt.cout, rt.fwd == "s3")], 0, rt.cout, rt.cin, rt.H) and rt.bww == "s3" \
+                and one_blocked(rt.bwd, 0, rt.cin, rt.cout, rt.H)
+        for t, pn in plan.producer.items():
+            cons, C = plan.consumers[t], plan.ch[t]
+            prod, con = self.convs.get(pn), self.convs.get(cons[0]) if len(cons) == 1 else None
+            if prod is None or con is None or t == plan.out or (con.s0, con.up0, con.s1) != (t, False, None) or C % 16 or _bwd_bounds(C) != [0, C]:
+                continue
+            # the consumer: forward (reads t), weight gradient (x = t), fused backward-data (mask t, writes DZ[t]).  A few-output-channel conv (the
+            # flow conv, networks.py:211,257): k_conv3d_k3_fewout / k_fewch_bwd_weight_h / k_conv3d_k3_kpack take the layout flags (round 6, late)
+            if not (plain(con) if con.cout > 4 else BLOCKED_LAST and C == 16 and FEWCH_H and con.fwd == "fewout" and con.bww == "fewch" and
+                    L.vxm_conv3d_k3_fwd_layout_ok(_ALIGNED, con.cout, con.cout * con.D * con.H * con.W, None, 0, 0, _ALIGNED, C, *con.geom)):
+                continue
+            # the producer: forward (writes t), weight gradient (dz = DZ[t]), backward-data (reads DZ[t])
+            if not prod.feeds_inputs and (plain(prod) if not prod.up0 else prod.s1 is not None and prod.up_fused and prod.fwd == "s3u" and prod.low_s3u
+                                          and prod.bww == "s3u+s3" and one_blocked(prod.skip_bwd, prod.c0, prod.cin, prod.cout, prod.H)):
+                out.add(t)
+        return frozenset(out)
+
+    @cached_property
+    def flags(self):
+        """Per conv op, the layout flags and hints of its launches: (forward `lay`, does its output get a sign tensor, `lay` of the weight
+        gradient, `lay` of the backward-data, does the fused backward-data read the sign tensor of s0 as its mask).
+        SNAKE: consecutive full-resolution split launches walk their tensors in alternating directions, forward and backward (S3_REVERSE_TILES)."""
+        blocked, out = self.blocked, {}
+        walked_back, dz_back = set(), set()      # tensors whose producer / whose gradient's producer walked its tiles from the end
+        for n, rt in self.convs.items():
+            x_blk, y_blk = rt.s0 in blocked, rt.dst in blocked
+            lay = (S3_IN0_BLOCKED if x_blk else 0) | (S3_OUT_BLOCKED if y_blk else 0)
+            if SNAKE and not (rt.up0 or rt.c1 or rt.feeds_inputs or rt.lvl or rt.s0 in walked_back) and rt.cout > 4 and rt.fwd == "s3":
+                lay |= S3_REVERSE_TILES
+                walked_back.add(rt.dst)
+            # the one reader of a blocked activation's sign is the backward-data epilogue of its consumer (a blocked split launch, or it
+            # would not be in `blocked`): one byte per four channels and voxel instead of the fp32 tensor there
+            signs = SIGNS and y_blk and rt.slope != 1.0 and rt.cout % 8 == 0 and s3_pieces() == 2
+            out[n] = [lay, signs, (S3_IN0_BLOCKED if x_blk else 0) | (S3_IN1_BLOCKED if y_blk else 0), S3_IN0_BLOCKED if y_blk else 0, False]
+        for n in sorted(self.convs, reverse=True):
+            rt = self.convs[n]
+            if not rt.fuse:
+                continue
+            one_split = rt.bwd == [(0, rt.cin, True)]
+            if SNAKE and rt.lvl == 0 and rt.dst not in dz_back and one_split:
+                out[n][3] |= S3_REVERSE_TILES          # (dropped by conv_bwd_data when the launch is not a split kernel's)
+                dz_back.add(rt.s0)
+            if rt.s0 in blocked:
+                out[n][3] |= S3_OUT_BLOCKED
+                out[n][4] = rt.pslope != 1.0 and len(rt.bwd) == 1 and (rt.cout <= 4 or one_split)
+        return {n: tuple(v) for n, v in out.items()}
+
+
+def _route_plan(plan, B, shape3):
+    """The route table of `plan` at batch B and volume shape3, cached on the plan under every switch a route reads"""
+    key = (B, tuple(shape3), FP32_ENGINE, S3U, S3_UP, SPLIT_48, BLOCKED, BLOCKED_LAST, FEWCH_H, SNAKE, SIGNS)
+    cache = plan.__dict__.setdefault("_route_cache", {})
+    return cache[key] if key in cache else cache.setdefault(key, _RouteTable(plan, B, shape3))
+
+
 def _s3_jobs(plan, params, B, shape3, with_backward, input_grads):
     """The split-kernel operators one pass over `plan` will ask for (forward operator of every eligible conv; for a training step
     the adjoints `conv_bwd_data` launches), so that they are packed in ONE launch.  A job listed here and not used costs a few
     microseconds; one not listed is packed on demand."""
-    jobs = []
-    for op in plan.ops:
-        if op["kind"] != "conv":
-            continue
-        s0, up0, s1 = op["src"]
-        w = params[2 * op["k"]]
-        cout, c0 = plan.ch[op["dst"]], plan.ch[s0]
-        c1 = plan.ch[s1] if s1 is not None else 0
-        if s0 < plan.n_inputs:
-            c0, c1 = sum(plan.ch[i] for i in range(plan.n_inputs)), 0 if plan.n_inputs == 1 else plan.ch[1]
-            c0 -= c1
-        D, H, W = _dims(shape3, plan.lvl[op["dst"]])
-        if cout > 4 and not (up0 and s3u_route(c0, c1, cout, B, D, H, W)) and s3_route(c0, up0, c1, cout, B, D, H, W):
-            jobs.append((w, 0, c0 + c1, False, c0))
-        if not with_backward or (s0 < plan.n_inputs and not input_grads):
-            continue
-        if up0:
-            # UnetFn.backward: the upsampled segment goes straight onto the low-resolution tensor when one of the two fused kernels takes the
-            # shape (then only the skip segment needs an adjoint here); otherwise the adjoint of the WHOLE virtual concat runs at this level
-            # (round 5: that pack was missing from the list, and was built on demand in the middle of the backward-data chain -- 0.23 ms behind
-            # the persistent blocks of the weight gradients, every step, at the 40x48x56 level of the default U-Net)
-            V = D * H * W
-            up_fused = plan.ops[plan.producer[s0]]["kind"] == "conv" and len(plan.consumers[s0]) == 1 if s0 in plan.producer else False
-            low = up_fused and (s3u_bwd_low_route(c0, cout, B, D, H, W) or
-                                bool(_lib.lib().vxm_conv3d_k3_up_bwd_low_ok(256, cout * V, c0, cout, B, D, H, W)))     # (256: any 16-byte aligned address)
-            ranges = ([(c0, c1)] if s1 is not None else []) if low else [(0, c0 + c1)]
-            if low and s1 is not None and up_fused and s3u_bwd_data_route(c0, c1, cout, B, D, H, W):
-                ranges = []                                         # k_s3u_bwd_pc computes the skip segment's gradient too (its operator: _prepack_plan, group B2)
-        else:
-            ranges = [(0, c0 + c1)]                                 # (first channel, count) handed to conv_bwd_data
-        for w_lo, cin in ranges:
-            bounds = _bwd_bounds(cin)
-            for lo, hi in zip(bounds[:-1], bounds[1:]):
-                if s3_route(cout, False, 0, hi - lo, B, D, H, W):
-                    jobs.append((w, w_lo + lo, w_lo + hi, True, cout))
-    return jobs
+    return [(params[2 * rt.k],) + args for rt in _route_plan(plan, B, shape3).convs.values()
+            for _, kind, args, _ in rt.packs(with_backward, input_grads) if kind == "s3"]
 
 
 def _prepack_plan(plan, params, B, shape3, with_backward, input_grads, dry=False, group=None):
-    """Every packed operator one pass over `plan` will ask for, built now, in three groups: "A" -- the split operators, in one batched launch
-    (_s3_jobs: weight scales + pre-split pieces, ~40 us); "B1" -- the fp32-MFMA operators of the forward convs the split engine does not take
-    (coarse levels: ~6 launches of 5 us); "B2" -- the collapsed operators of the cat([upsample, skip]) layers (forward: k_s3u_conv; backward-data
-    onto the low-resolution tensor: k_s3u_dlow) and the fp32-MFMA adjoints of the backward (~20 launches, ~150 us in a row).  group=None builds
-    all.  Returns the index of the first op that reads an operator of each group (A, B1, B2) -- len(ops) when none does; dry: only the indices.
+    """Every packed operator one pass over `plan` will ask for (_ConvRoute.packs), built now, in three groups: "A" -- the split operators, in one
+    batched launch (_s3_jobs: weight scales + pre-split pieces, ~40 us); "B1" -- the fp32-MFMA operators of the forward convs the split engine
+    does not take (coarse levels: ~6 launches of 5 us); "B2" -- the collapsed operators of the cat([upsample, skip]) layers (forward: k_s3u_conv;
+    backward-data onto the low-resolution tensor: k_s3u_dlow) and the fp32-MFMA adjoints of the backward (~20 launches, ~150 us in a row).
+    group=None builds all.  A guess that turns out unused costs its launch on the second stream; one that is missing is packed on demand.
+    Returns the index of the first op that reads an operator of each group (A, B1, B2) -- len(ops) when none does; dry: only the indices.
     Round 6: the groups have their own events.  In the default U-Net the first reader of A is the second layer (op 2), of B1 the first
     coarse-level conv (op 6), of B2 the first cat([upsample, skip]) layer (op 11): with ONE event the main chain sat idle for 0.23 ms per
     replayed step behind the first layer's pooling, waiting for all 27 launches (rocprofv3 dispatch list, profiles/r06q_dispatch_graph.txt)."""
-    do_a, do_b1, do_b = (not dry) and group in (None, "A"), (not dry) and group in (None, "B1"), (not dry) and group in (None, "B2")
-    if do_a:
+    build = {"fp32": pack_weights_cached, "s3u": s3u_pack, "s3u_low": s3u_bwd_low_pack, "s3u_skip": s3u_bwd_skip_pack}
+    if not dry and group in (None, "A"):
         s3_prepack(_s3_jobs(plan, params, B, shape3, with_backward, input_grads))
-    first_a = first_b1 = first_b = len(plan.ops)
-    for n, op in enumerate(plan.ops):
-        if op["kind"] != "conv":
-            continue
-        s0, up0, s1 = op["src"]
-        w = params[2 * op["k"]]
-        cout, c0 = plan.ch[op["dst"]], plan.ch[s0]
-        c1 = plan.ch[s1] if s1 is not None else 0
-        if s0 < plan.n_inputs:
-            c0, c1 = sum(plan.ch[i] for i in range(plan.n_inputs)), 0 if plan.n_inputs == 1 else plan.ch[1]
-            c0 -= c1
-        D, H, W = _dims(shape3, plan.lvl[op["dst"]])
-        uses = cout > 4 and s3_route(c0, up0, c1, cout, B, D, H, W)
-        if up0 and cout > 4 and s3u_route(c0, c1, cout, B, D, H, W):
-            if do_b:
-                s3u_pack(w, c0, c1)
-            first_b = min(first_b, n)
-        elif uses:
-            first_a = min(first_a, n)
-        if do_b and up0 and with_backward and s3u_bwd_low_route(c0, cout, B, D, H, W) and plan.ops[plan.producer[s0]]["kind"] == "conv" \
-                and len(plan.consumers[s0]) == 1:
-            s3u_bwd_low_pack(w, c0, c0 + c1)
-            if s1 is not None and s3u_bwd_data_route(c0, c1, cout, B, D, H, W):
-                s3u_bwd_skip_pack(w, c0, c1)
-        # the fp32-MFMA operators of the convs the split engine does not take (coarse levels, first layer, flow head): packed here too, so
-        # that the main chain does not carry a 5 us pack launch in front of each of them.  A guess that turns out unused costs that launch on
-        # the second stream; one that is missing is packed on demand, as before.
-        if n > 0 and cout > 4 and not uses and not up0:      # (op 0 needs its operator at once: packed on demand on the main stream)
-            if do_b1:
-                pack_weights_cached(w, False)
-            first_b1 = min(first_b1, n)                       # the main stream must have joined the second one before this launch
-        if do_b and with_backward and s0 >= plan.n_inputs:
-            whole = not up0
-            for w_lo, cin_r in ([(0, c0 + c1)] if whole else ([(c0, c1)] if s1 is not None else [])):
-                bounds = _bwd_bounds(cin_r)
-                for lo, hi in zip(bounds[:-1], bounds[1:]):
-                    if not s3_route(cout, False, 0, hi - lo, B, D, H, W):
-                        pack_weights_cached(w, True, w_lo + lo, w_lo + hi)
-    return first_a, first_b1, first_b
+    first = {"A": len(plan.ops), "B1": len(plan.ops), "B2": len(plan.ops)}
+    for n, rt in _route_plan(plan, B, shape3).convs.items():
+        for grp, kind, args, in_forward in rt.packs(with_backward, input_grads):
+            if in_forward and grp is not None:
+                first[grp] = min(first[grp], n)      # the main stream must have joined the second one before this launch
+            if not dry and grp in ("B1", "B2") and group in (None, grp):
+                build[kind](params[2 * rt.k], *args)
+    return first["A"], first["B1"], first["B2"]
 
 
 def _blocked_tensors(plan, B, shape3):
-    """Which activations of the fused U-Net are kept CHANNEL-BLOCKED ([B][C/8][D][H][W][8], include/vxm_hip.h VXM_S3_*_BLOCKED) instead of
-    NCDHW.  The tensors never leave the engine, so their layout is its own business; a haloed row of a blocked tensor is one contiguous run
-    and the split kernels, which are bound by the vector L1's sector requests, stage it 15 - 20 % faster.  A tensor t
-    qualifies when every kernel that writes or reads t, or the gradient DZ[t] (which takes the same layout), is a split kernel with a
-    blocked variant at this shape: t is the output of a ConvBlock, read by exactly one plain ConvBlock (forward, weight gradient, and the
-    fused backward-data that produces DZ[t] with t as its mask), and its producer's backward (weight gradient and backward-data, which read
-    DZ[t]) runs on the split kernels too.  In the default VxmDense U-Net: the outputs of remaining[0] and remaining[1]."""
-    if not (BLOCKED and split_engine() and s3_pieces() == 2):
-        return frozenset()
-    key = (B, tuple(shape3), FP32_ENGINE, S3U, S3_UP, SPLIT_48, BLOCKED_LAST, FEWCH_H)          # (the route predicates below depend on these switches)
-    cache = plan.__dict__.setdefault("_blocked_cache", {})
-    if key in cache:
-        return cache[key]
-    L = _lib.lib()
-    out = set()
-
-    def plain_ok(cin, cout, D, H, W):
-        """forward-type launch cin -> cout of a plain single-segment tensor on an 8-row split instance"""
-        return cout > 4 and s3_route(cin, False, 0, cout, B, D, H, W) and bool(L.vxm_conv3d_k3_s3_layout_ok(cin, 0, 0, cout, H, 2))
-
-    for t, pn in plan.producer.items():
-        prod = plan.ops[pn]
-        cons = plan.consumers[t]
-        if prod["kind"] != "conv" or t == plan.out or len(cons) != 1:
-            continue
-        cop = plan.ops[cons[0]]
-        if cop["kind"] != "conv" or tuple(cop["src"]) != (t, False, None):
-            continue
-        C, cc = plan.ch[t], plan.ch[cop["dst"]]
-        D, H, W = _dims(shape3, plan.lvl[t])
-        if C % 16 or _bwd_bounds(C) != [0, C]:
-            continue
-        # the consumer: forward (reads t), weight gradient (x = t), fused backward-data (mask t, writes DZ[t])
-        if cc <= 4:
-            # a few-output-channel conv (the flow conv, networks.py:211,257): k_conv3d_k3_fewout / k_fewch_bwd_weight_h / k_conv3d_k3_kpack take the
-            # layout flags (round 6, late); the *_ok predicates only look at alignment, which every torch allocation has (a stand-in address)
-            V = D * H * W
-            if not (BLOCKED_LAST and C == 16 and FEWCH_H and L.vxm_conv3d_k3_fewout_ok(256, C * V, 256, cc * V, C, cc, W)
-                    and L.vxm_conv3d_k3_fewch_bwd_weight_ok(256, C, C * V, None, 0, 0, 256, cc * V, cc, 2, W)
-                    and L.vxm_conv3d_k3_fwd_layout_ok(256, cc, cc * V, None, 0, 0, 256, C, B, D, H, W)):
-                continue
-        elif not (plain_ok(C, cc, D, H, W) and L.vxm_conv3d_k3_s3_bwd_weight_ok(C, cc, B, D, H, W) and plain_ok(cc, C, D, H, W)):
-            continue
-        # the producer: forward (writes t), weight gradient (dz = DZ[t]), backward-data (reads DZ[t])
-        s0, up0, s1 = prod["src"]
-        if s0 < plan.n_inputs:
-            continue
-        c0 = plan.ch[s0]
-        c1 = plan.ch[s1] if s1 is not None else 0
-        if up0:
-            up_fused = plan.ops[plan.producer[s0]]["kind"] == "conv" and len(plan.consumers[s0]) == 1
-            if not (s1 is not None and up_fused and s3u_route(c0, c1, C, B, D, H, W) and s3u_bwd_low_route(c0, C, B, D, H, W)
-                    and s3u_bwd_weight_route(c0, C, B, D, H, W) and L.vxm_conv3d_k3_s3_bwd_weight_ok(c1, C, B, D, H, W)
-                    and _bwd_bounds(c1) == [0, c1] and plain_ok(C, c1, D, H, W)):
-                continue
-        else:
-            if s1 is not None or _bwd_bounds(c0) != [0, c0]:
-                continue
-            if not (plain_ok(c0, C, D, H, W) and L.vxm_conv3d_k3_s3_bwd_weight_ok(c0, C, B, D, H, W) and plain_ok(C, c0, D, H, W)):
-                continue
-        out.add(t)
-    cache[key] = frozenset(out)
-    return cache[key]
+    """ids of the activations of the fused U-Net that are kept channel-blocked (_RouteTable.blocked)"""
+    return _route_plan(plan, B, shape3).blocked
 
 
 class UnetFn(torch.autograd.Function):
@@ -1323,12 +1368,11 @@ class UnetFn(torch.autograd.Function):
         ready = [None, None, None]               # events: the operators of group A / B1 / B2 are built (second stream, in that order)
         first = [len(plan.ops)] * 3
         packs_late = False
-        want_bwd = any(ctx.needs_input_grad[1:])
+        want_bwd, want_in = any(ctx.needs_input_grad[1:]), any(ctx.needs_input_grad[1:1 + plan.n_inputs])
         if split_engine():
             # The packed operators (weight scales, pre-split pieces, collapsed upsample operators: ~27 small launches, 0.2 ms in a row) are
             # rebuilt once per optimiser step.  They go to the second stream and run beside the layers that do not read them; the main stream
             # waits for each GROUP (_prepack_plan) in front of the first launch that reads it.
-            want_bwd, want_in = any(ctx.needs_input_grad[1:]), any(ctx.needs_input_grad[1:1 + plan.n_inputs])
             if OVERLAP_SMALL_LEVELS:
                 main, side = torch.cuda.current_stream(dev), _side_stream(dev)
                 fork = torch.cuda.Event()
@@ -1357,13 +1401,12 @@ class UnetFn(torch.autograd.Function):
                     # lists r06r / r06s), and the second layer then waited 82 us for these two launches
                     _prepack_plan(plan, params, B, shape3, want_bwd, want_in, group="A")
             else:
-                packs_late = False
                 _prepack_plan(plan, params, B, shape3, want_bwd, want_in)
                 _adopt_fresh_packs(None)
-        blocked = _blocked_tensors(plan, B, shape3)
+        table = _route_plan(plan, B, shape3)
+        blocked = table.blocked
         SG = {}                      # tensor id -> sign tensor of a channel-blocked activation (S3_OUT_SIGNS / S3_MASK_SIGNS)
         PC = {}                      # tensor id -> 16-bit codes of its pooling (vxm_maxpool2_fwd_code), for the fused pooling backward + weight gradient
-        walked_back = set()          # tensors whose producer walked its tiles from the end (S3_REVERSE_TILES)
         for n_op, op in enumerate(plan.ops):
             if packs_late and n_op >= 1:
                 # (captured right behind the FIRST op: on this runtime a branch of a replayed graph starts once everything the main chain had
@@ -1384,22 +1427,16 @@ class UnetFn(torch.autograd.Function):
                 s0, up0, s1 = op["src"]
                 w, b = params[2 * op["k"]], params[2 * op["k"] + 1]
                 x0, x1 = T[s0], (T[s1] if s1 is not None else None)
-                lay = (S3_IN0_BLOCKED if s0 in blocked else 0) | (S3_OUT_BLOCKED if dst in blocked else 0)
-                if SNAKE and not up0 and s1 is None and s0 >= plan.n_inputs and plan.lvl[dst] == 0 and plan.ch[dst] > 4 and s0 not in walked_back \
-                        and s3_route(plan.ch[s0], False, 0, plan.ch[dst], B, D, H, W):
-                    lay |= S3_REVERSE_TILES
-                    walked_back.add(dst)
+                lay, signs = table.flags[n_op][:2]
                 sg = None
-                if SIGNS and want_bwd and dst in blocked and op["slope"] != 1.0 and plan.ch[dst] % 8 == 0 and s3_pieces() == 2:
-                    # the one reader of this activation's sign is the backward-data epilogue of its consumer (a blocked split launch, or it
-                    # would not be in `blocked`): one byte per four channels and voxel instead of the fp32 tensor there
+                if signs and want_bwd:
                     sg = SG[dst] = torch.empty((B, plan.ch[dst] // 4, D, H, W), dtype=torch.uint8, device=dev)
                 conv_forward(x0, plan.ch[s0], x0[0].numel(), up0, x1, plan.ch[s1] if s1 is not None else 0,
                              x1[0].numel() if x1 is not None else 0, w, b, out, plan.ch[dst] * V, plan.ch[dst], op["slope"], B, D, H, W, lay=lay, signs=sg)
             elif op["kind"] == "pool":
                 src = T[op["src"]]
                 sD, sH, sW = src.shape[2:]
-                if want_bwd and _pool_fusable(plan, op["src"], shape3, any(ctx.needs_input_grad[1:1 + plan.n_inputs]), blocked):
+                if want_bwd and _pool_fusable(plan, op["src"], shape3, want_in, blocked):
                     PC[op["src"]] = torch.empty((B, plan.ch[dst], sD // 2, sH // 2, sW // 2), dtype=torch.int16, device=dev)
                     call("vxm_maxpool2_fwd_code", ptr(src), src[0].numel(), ptr(out), ptr(PC[op["src"]]), B, plan.ch[dst], sD, sH, sW, stream())
                 else:
@@ -1419,7 +1456,7 @@ class UnetFn(torch.autograd.Function):
             torch.cuda.current_stream(dev).wait_event(ready[2])
         out = T.pop(plan.out)
         ctx.save_for_backward(out)
-        ctx.plan, ctx.T, ctx.params, ctx.shape3, ctx.B, ctx.blocked, ctx.SG, ctx.PC = plan, T, params, shape3, B, blocked, SG, PC
+        ctx.plan, ctx.T, ctx.params, ctx.shape3, ctx.B, ctx.table, ctx.SG, ctx.PC = plan, T, params, shape3, B, table, SG, PC
         # activations and parameters are held as plain attributes (the returned tensor alone goes through
         # save_for_backward, see above), so autograd's version-counter check is done by hand in backward
         # (inference tensors -- torch.inference_mode() -- carry no version counter and can never reach backward)
@@ -1428,7 +1465,8 @@ class UnetFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        plan, params, shape3, B, blocked, SG, PC = ctx.plan, ctx.params, ctx.shape3, ctx.B, ctx.blocked, ctx.SG, ctx.PC
+        plan, params, shape3, B, table, SG, PC = ctx.plan, ctx.params, ctx.shape3, ctx.B, ctx.table, ctx.SG, ctx.PC
+        blocked = table.blocked
         if ctx.T is None:
             raise RuntimeError("UnetFn: backward a second time: the saved activations were released by the first pass "
                                "(a retained graph is not supported by the fused engine)")
@@ -1443,19 +1481,9 @@ class UnetFn(torch.autograd.Function):
         ws = _Workspace(dev)
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev) if OVERLAP_SMALL_LEVELS else None
-        # The weight gradients run on a second stream beside the backward-data chain.  Their small reduction kernels (partials -> gw, gb) go to
-        # a THIRD stream: behind a contraction on the second stream, the few blocks of a reduction waited for the persistent blocks of the main
-        # stream's kernel to leave the chip -- and the next contraction waited with them (rocprofv3 trace, round 5: 450 - 585 us, three times per
-        # step; the second stream ended the step 0.45 ms after the main one).
-        # (same-box A/B after the change: 84.6 -> 83.2 pairs/s eager, 82.5 -> 81.3 replayed.  The contractions then share the chip with the main
-        # chain ALL the time, both slow down, and the main chain ends 0.38 ms later: the chip is saturated either way, the stalls were not idle
-        # capacity.  Kept behind VXM_BW_REDUCE_STREAM=1 with its measurement; default: reductions behind their contraction, as before.)
-        red = _side_stream(dev, 1) if (side is not None and BW_REDUCE_STREAM) else None
-        pending = []
-        ws_side = _Workspace(dev, deferred=pending if red is not None else None)
+        ws_side = _Workspace(dev)
         n_in = plan.n_inputs
         grads = [None] * (n_in + len(params))
-        dz_back = set()   # tensor ids whose gradient DZ[.] was written from the end (S3_REVERSE_TILES)
         DZ = {}      # tensor id -> gradient w.r.t. the pre-activation of its producing conv
         GP = {}      # pool-output id -> gradient w.r.t. the pooled tensor
         GS = {}      # tensor id -> (buffer, element offset, batch stride): skip-branch gradient view
@@ -1521,32 +1549,12 @@ class UnetFn(torch.autograd.Function):
                 # ---- conv
                 s0, up0, s1 = op["src"]
                 w, b = params[2 * op["k"]], params[2 * op["k"] + 1]
-                cout = plan.ch[dst]
-                c0 = plan.ch[s0]
-                c1 = plan.ch[s1] if s1 is not None else 0
-                cin = c0 + c1
+                rt = table.convs[n]
+                cout, c0, c1, cin = rt.cout, rt.c0, rt.c1, rt.cin
                 dz = DZ.pop(dst)
                 x0, x1 = T[s0], (T[s1] if s1 is not None else None)
-                if isinstance(dz, _PoolGrad):
-                    # first block, nothing behind it: weight / bias gradient from the pooling backward's operands in one launch (main stream: the
-                    # last launch of the pass, see last_on_main below)
-                    gw_sink, gb_sink = _claim_sink(w), _claim_sink(b)
-                    gw = gw_sink if gw_sink is not None else torch.empty_like(w)
-                    gb = gb_sink if gb_sink is not None else torch.empty_like(b)
-                    need = _lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(cin, cout, B, D, H, W)
-                    buf = ws.get(need)
-                    with _prof.region("k_fewch_bwd_weight_h+pool", flops=2.0 * 27 * cin * cout * B * V):
-                        call("vxm_conv3d_k3_fewch_bwd_weight_pool", ptr(x0), c0, x0[0].numel(), ptr(x1), c1, x1[0].numel() if x1 is not None else 0,
-                             ptr(dz.gskip), dz.gs_bs, ptr(dz.gpool), ptr(dz.code), dz.slope, ptr(gw), ptr(gb), ptr(buf), buf.numel(), B, D, H, W, 2, stream())
-                    grads[n_in + 2 * op["k"]] = None if gw_sink is not None else gw
-                    grads[n_in + 2 * op["k"] + 1] = None if gb_sink is not None else gb
-                    continue
-                if _RANGE_PROBE is not None:
+                if _RANGE_PROBE is not None:      # (never with a _PoolGrad: _pool_fusable)
                     _probe("gradient at conv %d (%d channels, level %d)" % (op["k"], cout, plan.lvl[dst]), dz, cout, dst in blocked)
-                # channel-blocked tensors (_blocked_tensors): the activation s0 of a plain conv and / or this conv's own output, whose DZ shares its layout
-                dz_blk, x_blk = dst in blocked, s0 in blocked
-                lay_w = (S3_IN0_BLOCKED if x_blk else 0) | (S3_IN1_BLOCKED if dz_blk else 0)
-                lay_d = S3_IN0_BLOCKED if dz_blk else 0
                 # parameter gradients go straight into the optimiser's flat bucket when one is attached
                 # (voxelmorph_amd.optim.FlatAdam): no per-tensor accumulate / copy launches
                 # The kernel OVERWRITES its destination: only the first gradient of a parameter since zero_grad() may land in
@@ -1555,6 +1563,17 @@ class UnetFn(torch.autograd.Function):
                 gw_sink, gb_sink = _claim_sink(w), _claim_sink(b)
                 gw = gw_sink if gw_sink is not None else torch.empty_like(w)
                 gb = gb_sink if gb_sink is not None else torch.empty_like(b)
+                grads[n_in + 2 * op["k"]:n_in + 2 * op["k"] + 2] = [None if gw_sink is not None else gw, None if gb_sink is not None else gb]
+                if isinstance(dz, _PoolGrad):
+                    # first block, nothing behind it: weight / bias gradient from the pooling backward's operands in one launch (main stream: the
+                    # last launch of the pass, see last_on_main below)
+                    buf = ws.get(_lib.lib().vxm_conv3d_k3_bwd_weight_workspace_bytes(cin, cout, B, D, H, W))
+                    with _prof.region("k_fewch_bwd_weight_h+pool", flops=2.0 * 27 * cin * cout * B * V):
+                        call("vxm_conv3d_k3_fewch_bwd_weight_pool", ptr(x0), c0, x0[0].numel(), ptr(x1), c1, x1[0].numel() if x1 is not None else 0,
+                             ptr(dz.gskip), dz.gs_bs, ptr(dz.gpool), ptr(dz.code), dz.slope, ptr(gw), ptr(gb), ptr(buf), buf.numel(), B, D, H, W, 2, stream())
+                    continue
+                # channel-blocked tensors (_blocked_tensors): the activation s0 of a plain conv and / or this conv's own output, whose DZ shares its layout
+                _, _, lay_w, lay_d, mask_signs = table.flags[n]
                 # the FIRST layer's weight gradient is the last launch of the pass (its dz is the last thing the backward-data chain produces, and
                 # when the inputs need no gradient nothing follows it): on the main stream it starts the moment that dz exists, beside whatever
                 # the second stream still has queued, instead of behind it (rocprofv3 trace, round 5: the step ended 0.38 ms after the main chain)
@@ -1571,23 +1590,10 @@ class UnetFn(torch.autograd.Function):
                         with torch.cuda.stream(side):
                             conv_bwd_weight(ws_side, x0, c0, x0[0].numel(), up0, x1, c1, x1[0].numel() if x1 is not None else 0, dz, cout,
                                             gw, gb, B, D, H, W, lay=lay_w)
-                            if pending:
-                                ev2 = torch.cuda.Event()
-                                ev2.record(side)
                         dz.record_stream(side)          # dz is released by the main-stream chain before the side stream may be done
                         for g, sink in ((gw, gw_sink), (gb, gb_sink)):
                             if sink is None:            # allocated on the main stream, written on the side stream
                                 g.record_stream(side)
-                        if pending:                     # the reductions of the contractions just launched: third stream, behind them
-                            red.wait_event(ev2)
-                            with torch.cuda.stream(red):
-                                for name, args, flags, keep in pending:
-                                    call(name, *args, flags, stream())
-                            for _, _, _, keep in pending:
-                                for t in keep:
-                                    if t is not None:
-                                        t.record_stream(red)
-                            pending.clear()
                     if DW_ORDER == "after" or (DW_ORDER != "before" and torch.cuda.is_current_stream_capturing()):
                         deferred_dw = launch_dw     # enqueued behind this op's backward-data launches (top of the next iteration)
                     else:
@@ -1595,28 +1601,21 @@ class UnetFn(torch.autograd.Function):
                 else:
                     conv_bwd_weight(ws, x0, c0, x0[0].numel(), up0, x1, c1, x1[0].numel() if x1 is not None else 0, dz, cout,
                                     gw, gb, B, D, H, W, lay=lay_w)
-                grads[n_in + 2 * op["k"]] = None if gw_sink is not None else gw
-                grads[n_in + 2 * op["k"] + 1] = None if gb_sink is not None else gb
-                feeds_inputs = s0 < n_in
-                if feeds_inputs and not any(ctx.needs_input_grad[1 + i] for i in range(n_in)):
+                if rt.feeds_inputs and not any(ctx.needs_input_grad[1 + i] for i in range(n_in)):
                     continue
-                fuse = (not up0) and s1 is None and (not feeds_inputs) and len(plan.consumers[s0]) == 1 \
-                    and plan.ops[plan.producer[s0]]["kind"] == "conv"
-                up_fused = up0 and plan.ops[plan.producer[s0]]["kind"] == "conv" and len(plan.consumers[s0]) == 1
-                if up_fused and (s3u_bwd_low_route(c0, cout, B, D, H, W) or
-                                 _lib.lib().vxm_conv3d_k3_up_bwd_low_ok(ptr(dz), cout * V, c0, cout, B, D, H, W)):
+                if rt.low is not None:
                     # upsampled segment: straight to the half-resolution gradient of the decoder block (stride-2 4x4x4 conv =
                     # conv backward + upsample_nearest3d_backward + leaky_relu_backward in one kernel: conv_s3u.hip k_s3u_dlow on the split
                     # engine, conv_fwd.hip k_conv3d_k3_dlow otherwise)
-                    pslope = plan.ops[plan.producer[s0]]["slope"]
+                    pslope = rt.pslope
                     lD, lH, lW = D // 2, H // 2, W // 2
                     dzl = torch.empty((B, c0, lD, lH, lW), dtype=dt, device=dev)
                     gxs = None
-                    if s1 is not None and s3u_bwd_data_route(c0, c1, cout, B, D, H, W):
+                    if rt.low == "s3u_pc":
                         # both products from one staging of dz (k_s3u_bwd_pc): the skip segment's gradient comes with it
                         gxs = torch.empty((B, c1, D, H, W), dtype=dt, device=dev)
                         s3u_bwd_data(dz, cout, w, c0, c1, dzl, T[s0] if pslope != 1.0 else None, pslope, gxs, B, D, H, W, lay=lay_d)
-                    elif s3u_bwd_low_route(c0, cout, B, D, H, W):
+                    elif rt.low == "s3u_dlow":
                         s3u_bwd_low(dz, cout, w, c0, cin, dzl, T[s0] if pslope != 1.0 else None, pslope, B, D, H, W, lay=lay_d)
                     else:
                         _need_split_kernel(lay_d, "backward-data onto the low-resolution tensor")
@@ -1636,23 +1635,18 @@ class UnetFn(torch.autograd.Function):
                             finish_conv_output(s1, g[0].view(-1)[g[1]:], g[2])
                     continue
                 gx = torch.empty((B, cin, D, H, W), dtype=dt, device=dev)
-                if fuse:   # dX * LeakyReLU'(y_prev) in the epilogue == DZ of the previous ConvBlock
-                    pslope = plan.ops[plan.producer[s0]]["slope"]
-                    rev = 0
-                    if SNAKE and plan.lvl[dst] == 0 and dst not in dz_back and _bwd_bounds(cin) == [0, cin] and s3_route(cout, False, 0, cin, B, D, H, W):
-                        rev = S3_REVERSE_TILES          # (dropped by conv_bwd_data when the launch is not a split kernel's)
-                        dz_back.add(s0)
-                    if x_blk and pslope != 1.0 and s0 in SG and _bwd_bounds(cin) == [0, cin] and (cout <= 4 or s3_route(cout, False, 0, cin, B, D, H, W)):
-                        conv_bwd_data(dz, cout, w, gx, cin, SG[s0], pslope, B, D, H, W, lay=lay_d | S3_OUT_BLOCKED | S3_MASK_SIGNS | rev)
+                if rt.fuse:   # dX * LeakyReLU'(y_prev) in the epilogue == DZ of the previous ConvBlock (lay_d: with S3_OUT_BLOCKED / S3_REVERSE_TILES)
+                    pslope = rt.pslope
+                    if mask_signs and s0 in SG:
+                        conv_bwd_data(dz, cout, w, gx, cin, SG[s0], pslope, B, D, H, W, lay=lay_d | S3_MASK_SIGNS)
                     else:
-                        conv_bwd_data(dz, cout, w, gx, cin, T[s0] if pslope != 1.0 else None, pslope, B, D, H, W,
-                                      lay=lay_d | (S3_OUT_BLOCKED if x_blk else 0) | rev)
+                        conv_bwd_data(dz, cout, w, gx, cin, T[s0] if pslope != 1.0 else None, pslope, B, D, H, W, lay=lay_d)
                     DZ[s0] = gx
                     continue
-                if x_blk:
+                if s0 in blocked:
                     raise RuntimeError("UnetFn: a channel-blocked activation reached the unfused backward-data path")
                 conv_bwd_data(dz, cout, w, gx, cin, None, 1.0, B, D, H, W, lay=lay_d)
-                if feeds_inputs:
+                if rt.feeds_inputs:
                     for i, sid in enumerate([s0] + ([s1] if s1 is not None else [])):
                         lo = 0 if i == 0 else c0
                         grads[sid] = gx[:, lo:lo + plan.ch[sid]]
@@ -1678,8 +1672,6 @@ class UnetFn(torch.autograd.Function):
             # side-stream launches that are still writing parameter gradients
             if side is not None:
                 main.wait_stream(side)          # gradients (and the activations the side stream read) are final past this point
-                if red is not None:
-                    main.wait_stream(red)
         return (None,) + tuple(grads)
 
 
