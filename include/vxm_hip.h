@@ -600,6 +600,33 @@ int vxm_jacdet2d(const float* disp, float* det, int64_t* stats, int B, int H, in
  * shape it rejects */
 int vxm_jacdet3d_planes(int D, int H, int W);
 
+/* ---- mutual information (csrc/mi.hip): the global soft (Parzen-window) mutual information image loss for pairs of different contrast.
+ * The reference has it on its TensorFlow side only, voxelmorph/tf/losses.py:352-367, and that file shows the wrapper alone (loss =
+ * -volumes(y_true, y_pred) of a class of another package).  The algorithm is therefore fixed HERE, as this project's restatement of the
+ * formulation cited there (Guo's thesis; Hoffmann et al., SynthMorph); no bit parity with that other package is claimed.
+ *
+ *   per sample, flattened to N values (channels included):   a = clamp(I, min_clip, max_clip), b = clamp(J, min_clip, max_clip)
+ *   wa[n, k] = exp(-alpha (a[n] - c[k])^2) / sum_k' exp(-alpha (a[n] - c[k'])^2), wb likewise on b        (K centres c, strictly increasing)
+ *   pab = wa^T wb / N (K x K),   pa[k] = mean_n wa[n, k],   pb likewise,   papb = pa (x) pb + eps,   eps = 1e-7
+ *   MI = sum_{a, b} pab log(pab / papb + eps),   loss = -mean over the batch of MI
+ *
+ * The smallest squared distance is subtracted in the exponents (the same function; the denominator never underflows).  A NaN voxel makes
+ * the loss NaN, +-Inf is clamped.  2 <= K <= 32 (VXM_ERR_UNSUPPORTED otherwise); local (patch-wise) MI is not implemented.
+ * centres: K floats in HOST memory, passed on by value (the launches can be captured); alpha = 1 / (2 sigma^2).
+ * Forward: one pass over I, J accumulates per-workgroup K x K partials of wa^T wb on the fp32 matrix pipe, two small launches add them in a
+ * fixed order in float64 and leave in `state` (VXM_MI_STATE_FLOATS floats per sample, kept for backward) G = dLoss_b/dpab (32 x 32, row a)
+ * and the vectors dLoss_b/dpa, dLoss_b/dpb, with Loss_b = -MI_b.  work: the byte count of the workspace query (VXM_ERR_WORKSPACE
+ * below it), O(workgroups x K^2) and bounded in N: no buffer of N x K exists.  The chunk query returns the voxels one forward workgroup
+ * takes for N (tests: which sizes end on a partial chunk).  Backward: one pass recomputes the weights and writes gI = dL/dI and / or
+ * gJ = dL/dJ (either may be NULL), zero where the clamp was active.  No floating-point atomics: bit-reproducible. */
+#define VXM_MI_STATE_FLOATS (32 * 32 + 2 * 32)
+int64_t vxm_mi_chunk(int64_t N);
+size_t vxm_mi_workspace_bytes(int B, int64_t N, int K);
+int vxm_mi_fwd(const float* I, const float* J, const float* centres, int K, double alpha, float min_clip, float max_clip, float* loss,
+               float* state, void* work, size_t work_bytes, int B, int64_t N, void* stream);
+int vxm_mi_bwd(const float* I, const float* J, const float* centres, int K, double alpha, float min_clip, float max_clip, const float* state,
+               const float* gloss, float* gI, float* gJ, int B, int64_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,7 +49,8 @@ _FLAGS = [
     ('--int-steps', dict(type=int, default=7, help='scaling-and-squaring steps, 0 = no integration [7]')),
     ('--int-downsize', dict(type=int, default=2, help='integrate the field at 1/N of the image resolution [2]')),
     ('--bidir', dict(action='store_true', help='also warp the target onto the source and average both image losses')),
-    ('--image-loss', dict(default='mse', help="'mse' or 'ncc' [mse]")),
+    ('--image-loss', dict(default='mse', help="'mse', 'ncc' or 'mi' (mutual information, for pairs of different contrast) [mse]")),
+    ('--mi-bins', dict(type=int, default=32, help='intensity bins of the mutual information loss, 2 .. 32 [32]')),
     ('--lambda', dict(type=float, dest='weight', default=0.01, help='weight of the smoothness (Grad) term [0.01]')),
     ('--save-every', dict(type=int, default=20, help='epochs between checkpoints [20, as the reference]')),
 ]
@@ -111,8 +112,10 @@ def main(argv=None):
         image_loss = vxm.losses.NCC().loss
     elif args.image_loss == 'mse':
         image_loss = vxm.losses.MSE().loss
+    elif args.image_loss == 'mi':
+        image_loss = vxm.losses.MutualInformation(nb_bins=args.mi_bins).loss
     else:
-        raise ValueError('Image loss should be "mse" or "ncc", but found "%s"' % args.image_loss)
+        raise ValueError('Image loss should be "mse", "ncc" or "mi", but found "%s"' % args.image_loss)
     losses = [image_loss, image_loss] if args.bidir else [image_loss]
     weights = [0.5, 0.5] if args.bidir else [1.0]
     losses.append(vxm.losses.Grad('l2', loss_mult=args.int_downsize).loss)

@@ -43,7 +43,8 @@ _FLAGS = [
     ('--dec', dict(type=int, nargs='+', help='U-Net decoder features [32 32 32 32 32 16 16]')),
     ('--int-steps', dict(type=int, default=7, help='scaling-and-squaring steps [7]')),
     ('--int-downsize', dict(type=int, default=2, help='integrate the field at 1/N of the image resolution [2]')),
-    ('--image-loss', dict(default='mse', help="'mse' or 'ncc' [mse]")),
+    ('--image-loss', dict(default='mse', help="'mse', 'ncc' or 'mi' (mutual information, for pairs of different contrast) [mse]")),
+    ('--mi-bins', dict(type=int, default=32, help='intensity bins of the mutual information loss, 2 .. 32 [32]')),
     ('--grad-loss-weight', dict(type=float, default=0.01, help='weight of the smoothness term (lambda) [0.01]')),
     ('--dice-loss-weight', dict(type=float, default=0.01, help='weight of the Dice term (gamma) [0.01]')),
     ('--save-every', dict(type=int, default=20, help='epochs between checkpoints [20, as the reference]')),
@@ -99,8 +100,10 @@ def main(argv=None):
         image_loss = vxm.losses.NCC().loss
     elif args.image_loss == 'mse':
         image_loss = vxm.losses.MSE().loss
+    elif args.image_loss == 'mi':
+        image_loss = vxm.losses.MutualInformation(nb_bins=args.mi_bins).loss
     else:
-        raise ValueError('Image loss should be "mse" or "ncc", but found "%s"' % args.image_loss)
+        raise ValueError('Image loss should be "mse", "ncc" or "mi", but found "%s"' % args.image_loss)
     losses = [image_loss, vxm.losses.Grad('l2', loss_mult=args.int_downsize).loss, vxm.losses.Dice().loss]
     weights = [1.0, args.grad_loss_weight, args.dice_loss_weight]
 

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvxm_hip.so")
 
 _c = ctypes
-_P, _I, _L, _F, _S = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
+_P, _I, _L, _F, _S, _D = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t, _c.c_double
 
 
 class Bf16PackJob(_c.Structure):
@@ -164,6 +164,10 @@ SIGNATURES = {
     "vxm_jacdet3d": [_P, _P, _P, _I, _I, _I, _I, _P],
     "vxm_jacdet2d": [_P, _P, _P, _I, _I, _I, _P],
     "vxm_jacdet3d_planes": [_I, _I, _I],
+    "vxm_mi_chunk": [_L],
+    "vxm_mi_workspace_bytes": [_I, _L, _I],
+    "vxm_mi_fwd": [_P, _P, _P, _I, _D, _F, _F, _P, _P, _P, _S, _I, _L, _P],
+    "vxm_mi_bwd": [_P, _P, _P, _I, _D, _F, _F, _P, _P, _P, _P, _I, _L, _P],
 }
 _RESTYPES = {
     "vxm_workspace_bytes": _S,
@@ -181,6 +185,8 @@ _RESTYPES = {
     "vxm_conv3d_k3_s3u_bwd_low_packed_bytes": _S,
     "vxm_conv3d_k3_s3u_bwd_skip_packed_bytes": _S,
     "vxm_conv3d_k3_s3u_bwd_weight_workspace_bytes": _S,
+    "vxm_mi_chunk": _L,
+    "vxm_mi_workspace_bytes": _S,
 }
 
 _lib = None

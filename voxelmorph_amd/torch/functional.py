@@ -347,6 +347,50 @@ class NCCWinFn(torch.autograd.Function):
         return gI, gJ, None
 
 
+class MIFn(torch.autograd.Function):
+    """MutualInformation.loss: the global soft (Parzen-window) mutual information of include/vxm_hip.h ("mutual information"; the
+    reference has the loss on its TensorFlow side only, voxelmorph/tf/losses.py:352-367).  `centres`: tuple of K floats; `alpha` =
+    1 / (2 sigma^2); both inputs [B, ...] of one shape, every sample flattened (channels included)."""
+
+    @staticmethod
+    def forward(ctx, y_true, y_pred, centres, alpha, min_clip, max_clip):
+        require_device(y_true, y_pred)
+        I, J = _c(y_true), _c(y_pred)
+        if I.shape != J.shape or I.dim() < 2 or I.numel() == 0:
+            raise ValueError("MutualInformation: expected two [B, ...] tensors of one shape with at least 2 dimensions, got %s / %s"
+                             % (tuple(y_true.shape), tuple(y_pred.shape)))
+        B = int(I.shape[0])
+        N = I.numel() // B
+        K = len(centres)
+        cen = (ctypes.c_float * K)(*centres)
+        geo = (ctypes.cast(cen, ctypes.c_void_p), K, float(alpha), float(min_clip), float(max_clip))
+        loss = torch.empty((), dtype=I.dtype, device=I.device)
+        state = torch.empty((B, 32 * 32 + 2 * 32), dtype=I.dtype, device=I.device)              # VXM_MI_STATE_FLOATS (include/vxm_hip.h)
+        nbytes = int(_lib.lib().vxm_mi_workspace_bytes(B, N, K))
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=I.device)
+        with _prof.region("mi_fwd", nbytes=8.0 * B * N):
+            call("vxm_mi_fwd", ptr(I), ptr(J), *geo, ptr(loss), ptr(state), ptr(work), nbytes, B, N, stream())
+        ctx.save_for_backward(I, J, state)
+        ctx.geo = (tuple(float(c) for c in centres), float(alpha), float(min_clip), float(max_clip))
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        I, J, state = ctx.saved_tensors
+        centres, alpha, lo, hi = ctx.geo
+        B = int(I.shape[0])
+        N = I.numel() // B
+        cen = (ctypes.c_float * len(centres))(*centres)
+        gI = torch.empty_like(I) if ctx.needs_input_grad[0] else None
+        gJ = torch.empty_like(J) if ctx.needs_input_grad[1] else None
+        if gI is None and gJ is None:
+            return (None,) * 6
+        with _prof.region("mi_bwd", nbytes=(8.0 + 4.0 * ((gI is not None) + (gJ is not None))) * B * N):
+            call("vxm_mi_bwd", ptr(I), ptr(J), ctypes.cast(cen, ctypes.c_void_p), len(centres), alpha, lo, hi, ptr(state), ptr(_c(gloss)),
+                 ptr(gI), ptr(gJ), B, N, stream())
+        return gI, gJ, None, None, None, None
+
+
 class GradLossFn(torch.autograd.Function):
     """Grad.loss (voxelmorph/torch/losses.py:102-135)."""
 

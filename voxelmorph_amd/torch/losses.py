@@ -2,6 +2,8 @@
 
 Every class keeps the reference's `loss(y_true, y_pred) -> 0-dim tensor` contract.
 """
+import math
+
 from . import functional as VF
 from . import planar as VP
 
@@ -35,6 +37,51 @@ class MSE:
 
     def loss(self, y_true, y_pred):
         return VF.MSEFn.apply(y_true, y_pred)
+
+
+class MutualInformation:
+    """Global soft (Parzen-window) mutual information for pairs of different contrast (T1 / T2, MR / CT).
+
+    The reference has this loss on its TensorFlow side only (voxelmorph/tf/losses.py:352-367), and that file shows the wrapper alone:
+    `loss = -volumes(y_true, y_pred)` of a class of another package.  The algorithm is therefore this project's restatement of the
+    formulation cited there (Guo's thesis; Hoffmann et al.), written out in include/vxm_hip.h and DESIGN.md; the float64 evaluation in the
+    test table is its arbiter.  No bit parity with that other package is claimed.
+
+    bin_centers: strictly increasing sequence of K floats, default linspace(min_clip, max_clip, nb_bins) with nb_bins = 32; 2 <= K <= 32.
+    sigma = sigma_ratio * mean(diff(bin_centers)).  Inputs: two fp32 device tensors [B, ...] of one shape, at least 2 dimensions; every
+    sample is flattened (channels included) and clamped to [min_clip, max_clip]; the loss is -mean over the batch of MI.  A NaN voxel
+    makes the loss NaN.  Local (patch-wise) mutual information and more than 32 bins are out of scope."""
+
+    MAX_BINS = 32
+
+    def __init__(self, bin_centers=None, nb_bins=None, sigma_ratio=0.5, min_clip=0.0, max_clip=1.0):
+        self.min_clip, self.max_clip = float(min_clip), float(max_clip)
+        if not self.min_clip <= self.max_clip:
+            raise ValueError("MutualInformation: min_clip %r above max_clip %r" % (min_clip, max_clip))
+        if bin_centers is None:
+            k = 32 if nb_bins is None else int(nb_bins)
+            if k != (32 if nb_bins is None else nb_bins) or not 2 <= k <= self.MAX_BINS:
+                raise ValueError("MutualInformation: nb_bins must be an integer in 2 .. %d, got %r" % (self.MAX_BINS, nb_bins))
+            step = (self.max_clip - self.min_clip) / (k - 1)
+            centres = [self.min_clip + step * i for i in range(k - 1)] + [self.max_clip]
+        else:
+            centres = [float(c) for c in bin_centers]
+            if nb_bins is not None and int(nb_bins) != len(centres):
+                raise ValueError("MutualInformation: nb_bins=%r but %d bin_centers" % (nb_bins, len(centres)))
+        if not 2 <= len(centres) <= self.MAX_BINS:
+            raise ValueError("MutualInformation: %d bins; 2 .. %d are implemented" % (len(centres), self.MAX_BINS))
+        if any(not math.isfinite(c) for c in centres) or any(b <= a for a, b in zip(centres, centres[1:])):
+            raise ValueError("MutualInformation: bin_centers must be finite and strictly increasing")
+        self.sigma_ratio = float(sigma_ratio)
+        sigma = self.sigma_ratio * (centres[-1] - centres[0]) / (len(centres) - 1)        # mean(diff(bin_centers))
+        if not (sigma > 0 and math.isfinite(sigma)):
+            raise ValueError("MutualInformation: sigma_ratio must be positive, got %r" % (sigma_ratio,))
+        self.bin_centers = tuple(centres)
+        self.sigma = sigma
+        self.alpha = 1.0 / (2.0 * sigma * sigma)
+
+    def loss(self, y_true, y_pred):
+        return VF.MIFn.apply(y_true, y_pred, self.bin_centers, self.alpha, self.min_clip, self.max_clip)
 
 
 class Dice:
