@@ -13,6 +13,13 @@
 // feeds up to 3 NCT MFMAs.  Inputs are staged in 16-channel chunks (18 units -> 5 K-steps, 90 % of the K slots used).
 // Backward-weight contracts over voxels: both operands are read from [voxel][16 channel] LDS tiles with the transposing
 // LDS read of gfx950 (ds_read_b64_tr_b16: a lane receives 4 consecutive VOXELS of one channel), K = 32 voxels of a W row.
+//
+// Non-finite activations (tests/test_gpu_bf16_exact.py): a NaN / +-Inf at voxel p of an input channel makes the clipped 3 x 3 x 3 box of
+// outputs around p non-finite and nothing else, as in a float64 evaluation -- with one difference.  The fifth K-step of a chunk has two
+// padded K slots (units 18, 19): their weights are zero and their B operand is the voxel of unit 0 (tap kd = 0, kw = 0, channels 0..7 of the
+// chunk; see xoff below), so a +-Inf in the FIRST 8 channels of a chunk meets a zero weight once more (0 x Inf = NaN) at the outputs
+// p + (1, {-1, 0, 1}, 1): those hold NaN where the reference has +-Inf.  Inside the reference's non-finite footprint, so the hot loop
+// is left alone.
 #include "conv_common.h"
 
 namespace {
