@@ -40,7 +40,7 @@ typedef enum {
 enum { VXM_INTERP_LINEAR = 0, VXM_INTERP_NEAREST = 1 };   /* SpatialTransformer mode, layers.py:11 */
 enum { VXM_PENALTY_L1 = 0, VXM_PENALTY_L2 = 1 };          /* Grad penalty, losses.py:98 */
 
-int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 503 = 0.5.3 (round 6; every 0.4 / 0.5.x entry point kept) */
+int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 505 = 0.5.5 (every 0.4 / 0.5.x entry point kept) */
 const char* vxm_last_error_string(void);
 
 /* ---- the two umbrella names SURVEY.md section 8b lists.  Every op has its own *_workspace_bytes() query next to it; this one dispatches
@@ -626,6 +626,24 @@ int vxm_mi_fwd(const float* I, const float* J, const float* centres, int K, doub
                float* state, void* work, size_t work_bytes, int B, int64_t N, void* stream);
 int vxm_mi_bwd(const float* I, const float* J, const float* centres, int K, double alpha, float min_clip, float max_clip, const float* state,
                const float* gloss, float* gI, float* gJ, int B, int64_t N, void* stream);
+
+/* ---- affine transforms (csrc/affine.hip): a matrix as a dense displacement field, optionally right-composed with a dense field.  The
+ * reference has this on its TensorFlow side: voxelmorph/tf/utils/utils.py:638-699 (affine_to_dense_shift with warp_right), :253-318 (compose:
+ * a matrix left of a dense field is this op with warp_right), voxelmorph/tf/layers.py:494-529 (AffineToDenseShift).  This is this project's
+ * restatement; no bit parity with that package is claimed.
+ *
+ * Fields are [B,3,D,H,W] fp32; axis a in {0,1,2} is D,H,W ('ij' indexing); channel a is the displacement along axis a in voxels.
+ * mat: [Bm,3,4] fp32 with Bm in {1, B} (Bm = 1: one matrix for the whole batch), a FULL matrix (identity = no motion, utils.py:694), not a
+ * "shift" matrix.  shift_center = 1: c[a] = 0.5 (S[a] - 1) (utils.py:678-680); 0: c = 0.  In fp32 with every operation rounded on its own
+ * (no FMA, no reciprocal):
+ *     q[k] = (float(i[k]) - c[k])                       then, with a right-composed field w (flow, nullable):  q[k] = q[k] + w[b,k,i]
+ *     x[a] = (((M[a,0] q[0]) + (M[a,1] q[1])) + (M[a,2] q[2])) + M[a,3]
+ *   fwd: shift[b,a,i] = x[a] - (float(i[a]) - c[a])
+ *   bwd: gflow[b,k,i] = ((M[0,k] gout[b,0,i]) + (M[1,k] gout[b,1,i])) + (M[2,k] gout[b,2,i])      (the gradient for the right-composed field)
+ * Results are bit-identical from run to run.  No allocation, no synchronisation, no workspace.  The gradient with respect to the matrix and
+ * the one-interpolation resampling of a volume by a matrix are not part of this ABI version. */
+int vxm_affine_shift3d_fwd(const float* mat, int Bm, const float* flow, float* shift, int B, int D, int H, int W, int shift_center, void* stream);
+int vxm_affine_shift3d_bwd(const float* mat, int Bm, const float* gout, float* gflow, int B, int D, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

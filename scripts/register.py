@@ -4,7 +4,10 @@
 (`LoadableModel.load`, modelio.py:69-77).  nii / nii.gz / mgz / npz / npy in, nii / nii.gz / npz / npy out (voxelmorph_amd/nifti.py: the
 reference's nibabel is not needed); the moved image and the warp are saved with the FIXED image's affine, as register.py:75,88-92 does;
 `--seg` additionally warps a label map with the bit-exact nearest-neighbour transformer, and `--jacobian`
-reports the fraction of voxels with a non-positive Jacobian determinant of the deformation (py/utils.py:473-516)."""
+reports the fraction of voxels with a non-positive Jacobian determinant of the deformation (py/utils.py:473-516).
+`--affine FILE` (a 3 x 4 or 4 x 4 voxel-space matrix, .npy or whitespace text, applied about the volume's centre) pre-aligns the moving image:
+the network sees the image resampled by the matrix, `--moved` (and `--seg`, nearest) is produced from the ORIGINAL image in one interpolation
+by the composed dense transform (the matrix left of the network's warp), which `--warp` saves."""
 import argparse
 import os
 import sys
@@ -48,6 +51,7 @@ def main(argv=None):
     p.add_argument('--warp', help='output warp deformation filename')
     p.add_argument('--seg', help='label map of the moving image to warp with nearest-neighbour interpolation')
     p.add_argument('--moved-seg', help='output filename of the warped label map')
+    p.add_argument('--affine', help='3 x 4 or 4 x 4 voxel-space matrix (.npy or whitespace text) that pre-aligns the moving image')
     p.add_argument('--jacobian', action='store_true', help='print the fraction of non-positive Jacobian determinants')
     p.add_argument('-g', '--gpu', default='0', help='GPU number (this path has no CPU fallback)')
     p.add_argument('--multichannel', action='store_true', help='volumes carry a trailing feature axis [*vol, C]')
@@ -73,13 +77,24 @@ def main(argv=None):
     model.to(dev)
     model.eval()
     with torch.no_grad():
-        moved, warp = model(moving, fixed, registration=True)
+        if args.affine:
+            sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+            from warp import load_affine
+            mat = torch.from_numpy(load_affine(args.affine)).to(dev)
+            _, net_warp = model(vxm.utils.transform(moving, mat), fixed, registration=True)
+            warp = vxm.utils.compose([mat, net_warp])                             # the matrix left of the dense field, as one dense transform
+            moved = vxm.utils.transform(moving, warp)                             # the original image at matrix (p + warp(p)): one interpolation
+        else:
+            moved, warp = model(moving, fixed, registration=True)
         save_vol((moved[0].permute(1, 2, 3, 0) if args.multichannel else moved).cpu().numpy().squeeze(), args.moved, fixed_affine)
         if args.warp:
             save_vol(warp.cpu().numpy().squeeze(), args.warp, fixed_affine)
         if args.seg:
             seg = load(args.seg)
-            out = vxm.layers.SpatialTransformer(seg.shape[2:], mode='nearest').to(dev)(seg, warp)
+            if args.affine:
+                out = vxm.utils.transform(seg, warp, interp_method='nearest')
+            else:
+                out = vxm.layers.SpatialTransformer(seg.shape[2:], mode='nearest').to(dev)(seg, warp)
             save_vol(out.cpu().numpy().squeeze(), args.moved_seg or (os.path.splitext(args.moved)[0] + '_seg.npz'), fixed_affine)
         if args.jacobian:
             print('non-positive Jacobian fraction: %.6f' % nonpositive_jacobian_fraction(warp[0]))

@@ -8,6 +8,7 @@ of `include/vxm_hip.h` (libvxm_hip.so).  No CPU or ATen fallback exists for the 
 from .torch import layers, losses, networks  # noqa: F401
 from .torch.networks import default_unet_features  # noqa: F401
 from . import torch  # noqa: F401
+from .torch import transforms as utils  # noqa: F401      (affine transforms: apply, compose, convert to dense, invert -- the reference's vxm.utils)
 from . import metrics, py  # noqa: F401                   (evaluation: device Dice / Jacobian, and the reference's vxm.py.utils path)
 from .torch.functional_bf16 import invalidate_packs  # noqa: F401
 from .graph import GraphedStep  # noqa: F401              (a training step as one hipGraph launch)

@@ -168,6 +168,8 @@ SIGNATURES = {
     "vxm_mi_workspace_bytes": [_I, _L, _I],
     "vxm_mi_fwd": [_P, _P, _P, _I, _D, _F, _F, _P, _P, _P, _S, _I, _L, _P],
     "vxm_mi_bwd": [_P, _P, _P, _I, _D, _F, _F, _P, _P, _P, _P, _I, _L, _P],
+    "vxm_affine_shift3d_fwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vxm_affine_shift3d_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {
     "vxm_workspace_bytes": _S,

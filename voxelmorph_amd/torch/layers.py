@@ -8,6 +8,7 @@ from torch import nn
 
 from . import functional as VF
 from . import planar as VP
+from . import transforms as VT
 
 _LINEAR_MODE = {1: 'linear', 2: 'bilinear', 3: 'trilinear'}
 
@@ -24,6 +25,10 @@ class SpatialTransformer(nn.Module):
     `grid` exists only for state-dict parity with the reference (it is in `state_dict()`, stripped by `LoadableModel.save`):
     the kernels compute voxel indices in registers, reproduce the reference's normalise / un-normalise round trip in fp32
     (`vxm_src_coord`) and never read the buffer.
+
+    `forward(src, trf)` also takes a matrix `trf` [Bm,3,4] / [Bm,4,4] (Bm in {1, B}; tf/layers.py:34-152): the volume is resampled on its own
+    grid about its centre (`shift_center=True`), in the transformer's mode -- the matrix becomes a dense field (csrc/affine.hip), which the
+    same kernel as for a dense `trf` applies.
     """
 
     def __init__(self, size, mode='bilinear'):
@@ -34,6 +39,11 @@ class SpatialTransformer(nn.Module):
         self.register_buffer('grid', _identity_grid(size))
 
     def forward(self, src, flow):
+        if flow.dim() == 3:                                   # a matrix
+            if src.dim() != 5:
+                raise NotImplementedError("SpatialTransformer: a matrix transform needs a 3-D volume [B,C,D,H,W]; 2-D affine transforms "
+                                          "are not implemented (DESIGN.md 4.12)")
+            return VT.transform(src, flow, interp_method=self.mode, shift_center=True)
         expected = tuple(self.grid.shape[2:])
         if tuple(flow.shape[2:]) != expected:
             raise RuntimeError("flow spatial shape %s does not match the transformer size %s" % (tuple(flow.shape[2:]), expected))
@@ -73,3 +83,36 @@ class ResizeTransform(nn.Module):
             return x
         resize = VP.Resize2dFn if x.dim() == 4 else VF.ResizeFn
         return resize.apply(x, self.factor)
+
+
+class AffineToDenseShift(nn.Module):
+    """A matrix [Bm,3,4] / [Bm,4,4] as a dense displacement field [Bm,3,*shape] (reference: tf/layers.py:494-529, utils.py:638-699)."""
+
+    def __init__(self, shape, shift_center=True):
+        super().__init__()
+        self.shape = tuple(int(s) for s in shape)
+        self.shift_center = shift_center
+
+    def forward(self, mat):
+        return VT.affine_to_dense_shift(mat, self.shape, shift_center=self.shift_center)
+
+
+class ComposeTransform(nn.Module):
+    """Composes a list of matrices and / or dense fields, given in the order of application, into one transform (reference:
+    tf/layers.py:319-375, utils.py:253-318); dense unless every entry is a matrix."""
+
+    def __init__(self, interp_method='linear', shift_center=True, shape=None):
+        super().__init__()
+        self.interp_method = interp_method
+        self.shift_center = shift_center
+        self.shape = shape
+
+    def forward(self, transforms):
+        return VT.compose(list(transforms), interp_method=self.interp_method, shift_center=self.shift_center, shape=self.shape)
+
+
+class InvertAffine(nn.Module):
+    """The inverse of an affine matrix [..., 3, 4] / [..., 4, 4], in closed form (reference: tf/layers.py:418-437)."""
+
+    def forward(self, mat):
+        return VT.invert_affine(mat)
