@@ -40,7 +40,7 @@ typedef enum {
 enum { VXM_INTERP_LINEAR = 0, VXM_INTERP_NEAREST = 1 };   /* SpatialTransformer mode, layers.py:11 */
 enum { VXM_PENALTY_L1 = 0, VXM_PENALTY_L2 = 1 };          /* Grad penalty, losses.py:98 */
 
-int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 505 = 0.5.5 (every 0.4 / 0.5.x entry point kept) */
+int vxm_version(void);                 /* 10000 major + 100 minor + patch of this ABI: 506 = 0.5.6 (every 0.4 / 0.5.x entry point kept) */
 const char* vxm_last_error_string(void);
 
 /* ---- the two umbrella names SURVEY.md section 8b lists.  Every op has its own *_workspace_bytes() query next to it; this one dispatches
@@ -644,6 +644,37 @@ int vxm_mi_bwd(const float* I, const float* J, const float* centres, int K, doub
  * the one-interpolation resampling of a volume by a matrix are not part of this ABI version. */
 int vxm_affine_shift3d_fwd(const float* mat, int Bm, const float* flow, float* shift, int B, int D, int H, int W, int shift_center, void* stream);
 int vxm_affine_shift3d_bwd(const float* mat, int Bm, const float* gout, float* gflow, int B, int D, int H, int W, void* stream);
+
+/* ---- probabilistic velocity field (csrc/prob.hip): the KL loss and the reparameterised sample of the reference's probabilistic diffeomorphic
+ * model, which it has on its TensorFlow side only: voxelmorph/tf/losses.py:247-349 (KL), voxelmorph/tf/networks.py:154-163, 230-232 (the two
+ * heads, their concat `flow_params`, the Sample layer).  This is this project's restatement on the torch-side layout.
+ *
+ * params: [B,6,D,H,W] fp32; channels 0..2 are the mean mu, channels 3..5 are ls = log sigma^2.  V = D H W, axis a in {0,1,2} has extent
+ * S_a >= 2 (VXM_ERR_BAD_SHAPE otherwise: the reference's mean over an empty slice is NaN), V < 2^31, lambda = prior_lambda (finite).
+ *
+ *   deg(i) = sum_a [(i_a > 0) + (i_a < S_a - 1)]          (the reference's conv of ones with the 6-neighbour filter, zero padded)
+ *   S_sig  = sum_{b,c,i} (lambda * deg(i) * exp(ls[b,c,i]) - ls[b,c,i])
+ *   S_a    = sum_{b,c,i : i_a < S_a-1} (mu[b,c,i+e_a] - mu[b,c,i])^2 ,    N_a = 3 B V (S_a - 1) / S_a   (an integer: the number of differences)
+ *   loss   = 1.5 * ( S_sig / (3 B V) + lambda * (0.5 / 3) * ((S_0/N_0 + S_1/N_1) + S_2/N_2) )
+ *   gls[b,c,i] = g * (lambda * deg(i) * exp(ls) - 1) / (2 B V)
+ *   gmu[b,c,i] = g * 0.5 * lambda * sum_a ( [i_a>0] (mu_i - mu_{i-e_a}) - [i_a<S_a-1] (mu_{i+e_a} - mu_i) ) / N_a
+ *
+ * Per-voxel terms are fp32 (expf, not the fast intrinsic; lambda rounded to fp32 there); the sums are per-workgroup partials in float64 that a
+ * second small launch adds in a fixed order; the last expression is evaluated in float64 in the order written and rounded to fp32 once.
+ * Backward: the constants 1 / (2 B V) and 0.5 lambda / N_a are formed in float64 on the host and rounded to fp32; g is read on the device.
+ * No floating-point atomics: results are bit-identical from run to run.  work: the byte count of the workspace query (VXM_ERR_WORKSPACE
+ * below it; 0 for a shape the calls refuse).  The launches allocate nothing, never synchronise and read nothing on the host.  Forward is
+ * one pass over the six planes; backward is one pass that writes all six gradient planes [B,6,D,H,W].
+ *
+ * Sample: eps, z, gz: [B,3,V] fp32, V = voxels per sample (any grid).  The noise is an INPUT: the definition stays deterministic.
+ *   fwd: z[b,c,i] = mu + expf(0.5f * ls) * eps
+ *   bwd: gparams [B,6,V] is WRITTEN (nothing is added into): gmu = gz,  gls = gz * (0.5f * expf(0.5f * ls)) * eps
+ * Pointwise; 16-byte accesses when V is a multiple of 4 and the four base pointers are 16-byte aligned, element by element otherwise. */
+size_t vxm_kl_workspace_bytes(int B, int D, int H, int W);
+int vxm_kl_fwd(const float* params, double prior_lambda, float* loss, void* work, size_t work_bytes, int B, int D, int H, int W, void* stream);
+int vxm_kl_bwd(const float* params, double prior_lambda, const float* gloss, float* gparams, int B, int D, int H, int W, void* stream);
+int vxm_sample_logvar_fwd(const float* params, const float* eps, float* z, int B, int64_t V, void* stream);
+int vxm_sample_logvar_bwd(const float* params, const float* eps, const float* gz, float* gparams, int B, int64_t V, void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,10 @@ _FLAGS = [
     ('--image-loss', dict(default='mse', help="'mse', 'ncc' or 'mi' (mutual information, for pairs of different contrast) [mse]")),
     ('--mi-bins', dict(type=int, default=32, help='intensity bins of the mutual information loss, 2 .. 32 [32]')),
     ('--lambda', dict(type=float, dest='weight', default=0.01, help='weight of the smoothness (Grad) term [0.01]')),
+    ('--use-probs', dict(action='store_true', help='train the probabilistic model (VxmDenseProbabilistic): KL loss instead of Grad, weighted by --lambda')),
+    ('--kl-lambda', dict(type=float, default=10, help='prior lambda of the KL loss, with --use-probs [10]')),
+    ('--image-sigma', dict(type=float, default=1.0, help='estimated image noise; the image loss is weighted by 1 / sigma^2 '
+                                                         '[1.0; 0.02 is recommended with --use-probs]')),
     ('--save-every', dict(type=int, default=20, help='epochs between checkpoints [20, as the reference]')),
 ]
 
@@ -96,7 +100,12 @@ def main(argv=None):
 
     enc = args.enc if args.enc else [16, 32, 32, 32]
     dec = args.dec if args.dec else [32, 32, 32, 32, 32, 16, 16]
-    if args.load_model:
+    if args.use_probs and args.load_model:
+        model = vxm.networks.VxmDenseProbabilistic.load(args.load_model, dev)
+    elif args.use_probs:
+        model = vxm.networks.VxmDenseProbabilistic(inshape=inshape, nb_unet_features=[enc, dec], bidir=args.bidir, int_steps=args.int_steps,
+                                                   int_downsize=args.int_downsize, src_feats=loader.channels, trg_feats=loader.channels)
+    elif args.load_model:
         model = vxm.networks.VxmDense.load(args.load_model, dev)
     else:
         # (the reference builds the model for one feature per image even with --multichannel and then fails in its first
@@ -118,7 +127,13 @@ def main(argv=None):
         raise ValueError('Image loss should be "mse", "ncc" or "mi", but found "%s"' % args.image_loss)
     losses = [image_loss, image_loss] if args.bidir else [image_loss]
     weights = [0.5, 0.5] if args.bidir else [1.0]
-    losses.append(vxm.losses.Grad('l2', loss_mult=args.int_downsize).loss)
+    # the image term carries 1 / sigma^2 (scripts/tf/train.py:83-94,172-178; --image-sigma 1.0 leaves the weights of the reference's torch script)
+    weights = [w / args.image_sigma ** 2 for w in weights]
+    if args.use_probs:
+        # the velocity field is regularised by its prior (KL on the 6-channel flow_params at the grid the heads run on) instead of Grad
+        losses.append(vxm.losses.KL(args.kl_lambda, inshape).loss)
+    else:
+        losses.append(vxm.losses.Grad('l2', loss_mult=args.int_downsize).loss)
     weights.append(args.weight)
 
     os.makedirs(args.model_dir, exist_ok=True)
@@ -132,8 +147,15 @@ def main(argv=None):
     static_in, static_true = [t.clone() for t in inputs], [t.clone() if torch.is_tensor(t) else t for t in y_true]
     terms = torch.zeros(len(losses) + 1, device=dev)
 
+    noise_rng = None
+    if args.use_probs:
+        # the sampler's noise is an input of the kernels: it lives in the static buffer model.noise, refilled before every step next to the
+        # batch (a captured step reads it by address); every rank draws its own stream
+        noise_rng = torch.Generator(device=dev).manual_seed(torch.initial_seed() + 7919 * (rank + 1))
+        model.draw_noise(noise_rng, batch=hi - lo)
+
     def forward_loss():
-        y_pred = model(*static_in)
+        y_pred = model(*static_in, noise=model.noise) if args.use_probs else model(*static_in)
         # train.py:205-212 (`loss += loss_function(y_true[n], y_pred[n]) * weights[n]`): products, sum and the per-epoch accumulators in one launch
         return vxm.losses.weighted_sum([fn(static_true[n], y_pred[n]) for n, fn in enumerate(losses)], weights, running=terms)
 
@@ -163,6 +185,8 @@ def main(argv=None):
                         raise RuntimeError('train.py: a non-tensor entry of y_true changed between batches (%r -> %r); the graphed step '
                                            'captured the first value' % (dst, src))
             fresh = True
+            if noise_rng is not None:
+                model.draw_noise(noise_rng)
             step()
             pace.mark()
         torch.cuda.synchronize()

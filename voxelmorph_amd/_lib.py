@@ -170,6 +170,11 @@ SIGNATURES = {
     "vxm_mi_bwd": [_P, _P, _P, _I, _D, _F, _F, _P, _P, _P, _P, _I, _L, _P],
     "vxm_affine_shift3d_fwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "vxm_affine_shift3d_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _P],
+    "vxm_kl_workspace_bytes": [_I, _I, _I, _I],
+    "vxm_kl_fwd": [_P, _D, _P, _P, _S, _I, _I, _I, _I, _P],
+    "vxm_kl_bwd": [_P, _D, _P, _P, _I, _I, _I, _I, _P],
+    "vxm_sample_logvar_fwd": [_P, _P, _P, _I, _L, _P],
+    "vxm_sample_logvar_bwd": [_P, _P, _P, _P, _I, _L, _P],
 }
 _RESTYPES = {
     "vxm_workspace_bytes": _S,
@@ -189,6 +194,7 @@ _RESTYPES = {
     "vxm_conv3d_k3_s3u_bwd_weight_workspace_bytes": _S,
     "vxm_mi_chunk": _L,
     "vxm_mi_workspace_bytes": _S,
+    "vxm_kl_workspace_bytes": _S,
 }
 
 _lib = None

@@ -1763,3 +1763,117 @@ def _resolve_decoder(plan, T, DZ, GC, tid, B, shape3, dt, dev):
         DZ[tid] = dz
     else:
         raise NotImplementedError("upsampling a non-conv tensor is not produced by Unet topologies")
+
+
+# --------------------------------------------------------------------------- probabilistic velocity field (csrc/prob.hip)
+def _params6(t, what):
+    if t.dim() != 5 or t.shape[1] != 6:
+        raise ValueError("%s: expected the 6-channel tensor [B,6,D,H,W] (mean, then log sigma^2) of a 3-D volume, got %s" % (what, tuple(t.shape)))
+
+
+class KLFn(torch.autograd.Function):
+    """KL.loss (voxelmorph/tf/losses.py:319-349) on params [B,6,D,H,W]: the definition of include/vxm_hip.h ("probabilistic velocity field")."""
+
+    @staticmethod
+    def forward(ctx, params, prior_lambda):
+        _params6(params, "KL")
+        if any(int(s) < 2 for s in params.shape[2:]):
+            raise ValueError("KL: every extent of the grid must be at least 2, got %s" % (tuple(params.shape[2:]),))
+        require_device(params)
+        p = _c(params)
+        B, _, D, H, W = p.shape
+        loss = torch.empty((), dtype=p.dtype, device=p.device)
+        nbytes = int(_lib.lib().vxm_kl_workspace_bytes(B, D, H, W))
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=p.device)
+        with _prof.region("kl_fwd", nbytes=24.0 * B * D * H * W):
+            call("vxm_kl_fwd", ptr(p), float(prior_lambda), ptr(loss), ptr(work), nbytes, B, D, H, W, stream())
+        ctx.save_for_backward(p)
+        ctx.prior_lambda = float(prior_lambda)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (p,) = ctx.saved_tensors
+        B, _, D, H, W = p.shape
+        gp = torch.empty_like(p)
+        with _prof.region("kl_bwd", nbytes=48.0 * B * D * H * W):
+            call("vxm_kl_bwd", ptr(p), ctx.prior_lambda, ptr(_c(gloss)), ptr(gp), B, D, H, W, stream())
+        return gp, None
+
+
+class SampleLogVarFn(torch.autograd.Function):
+    """z = mu + exp(ls / 2) * eps (the Sample layer of voxelmorph/tf/networks.py:230-232) on params [B,6,D,H,W] and caller-supplied noise
+    eps [B,3,D,H,W]; backward writes the whole [B,6,...] gradient (gmu = gz, gls = gz * 0.5 exp(ls / 2) * eps)."""
+
+    @staticmethod
+    def forward(ctx, params, eps):
+        _params6(params, "sample")
+        if tuple(eps.shape) != (params.shape[0], 3) + tuple(params.shape[2:]):
+            raise ValueError("sample: noise of shape %s does not fit parameters %s" % (tuple(eps.shape), tuple(params.shape)))
+        require_device(params, eps)
+        p, e = _c(params), _c(eps)
+        B, V = p.shape[0], p[0, 0].numel()
+        z = torch.empty_like(e)
+        call("vxm_sample_logvar_fwd", ptr(p), ptr(e), ptr(z), B, V, stream())
+        ctx.save_for_backward(p, e)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        p, e = ctx.saved_tensors
+        gp = torch.empty_like(p)
+        call("vxm_sample_logvar_bwd", ptr(p), ptr(e), ptr(_c(gz)), ptr(gp), p.shape[0], p[0, 0].numel(), stream())
+        return gp, None
+
+
+class ProbHeadsFn(torch.autograd.Function):
+    """The two 3-channel heads of the probabilistic model (voxelmorph/tf/networks.py:154-163: `flow` and `flow_logsigma`, then their concat)
+    on one U-Net output x: two launches of the conv_forward route, each writing its half of ONE [B,6,D,H,W] buffer through the destination's
+    batch stride (no cat).  Backward: two conv_bwd_weight calls (into the optimiser's flat bucket when one is attached, as UnetFn does) and two
+    conv_bwd_data calls whose results vxm_add2 sums.  Not part of the fused U-Net plan."""
+
+    @staticmethod
+    def forward(ctx, x, w_mu, b_mu, w_ls, b_ls):
+        _vol3(x, "probabilistic heads")
+        require_device(x, w_mu, b_mu, w_ls, b_ls)
+        x = _c(x)
+        B, cin, D, H, W = x.shape
+        for w in (w_mu, w_ls):
+            if tuple(w.shape) != (3, cin, 3, 3, 3):
+                raise ValueError("probabilistic heads: weight %s does not fit an input with %d channels (3 output channels, 3x3x3 kernels)"
+                                 % (tuple(w.shape), cin))
+        V = D * H * W
+        params = torch.empty((B, 6, D, H, W), dtype=x.dtype, device=x.device)
+        conv_forward(x, cin, cin * V, False, None, 0, 0, _c(w_mu), b_mu, params, 6 * V, 3, 1.0, B, D, H, W)
+        conv_forward(x, cin, cin * V, False, None, 0, 0, _c(w_ls), b_ls, params[:, 3:], 6 * V, 3, 1.0, B, D, H, W)
+        ctx.save_for_backward(x, w_mu, w_ls)
+        ctx.heads = (w_mu, b_mu, w_ls, b_ls)
+        return params
+
+    @staticmethod
+    def backward(ctx, gparams):
+        x, w_mu, w_ls = ctx.saved_tensors
+        B, cin, D, H, W = x.shape
+        V = D * H * W
+        gparams = _c(gparams)
+        # the conv backward kernels read a gradient whose batch stride is its own channel count: with one sample the two halves are that already
+        halves = [_c(gparams[:, :3]), _c(gparams[:, 3:])]
+        ws = _Workspace(x.device)
+        grads = [None] * 5
+        need_w = [ctx.needs_input_grad[1] or ctx.needs_input_grad[2], ctx.needs_input_grad[3] or ctx.needs_input_grad[4]]
+        for k, (w, b, dz) in enumerate(((ctx.heads[0], ctx.heads[1], halves[0]), (ctx.heads[2], ctx.heads[3], halves[1]))):
+            if not need_w[k]:
+                continue
+            gw_sink, gb_sink = _claim_sink(w), _claim_sink(b)
+            gw = gw_sink if gw_sink is not None else torch.empty_like(w)
+            gb = gb_sink if gb_sink is not None else torch.empty_like(b)
+            conv_bwd_weight(ws, x, cin, cin * V, False, None, 0, 0, dz, 3, gw, gb, B, D, H, W)
+            grads[1 + 2 * k:3 + 2 * k] = [None if gw_sink is not None else gw, None if gb_sink is not None else gb]
+        if ctx.needs_input_grad[0]:
+            ga, gb_ = torch.empty_like(x), torch.empty_like(x)
+            conv_bwd_data(halves[0], 3, _c(w_mu), ga, cin, None, 1.0, B, D, H, W)
+            conv_bwd_data(halves[1], 3, _c(w_ls), gb_, cin, None, 1.0, B, D, H, W)
+            gx = torch.empty_like(x)
+            call("vxm_add2", ptr(ga), ptr(gb_), ptr(gx), gx.numel(), stream())
+            grads[0] = gx
+        return tuple(grads)

@@ -84,6 +84,29 @@ class MutualInformation:
         return VF.MIFn.apply(y_true, y_pred, self.bin_centers, self.alpha, self.min_clip, self.max_clip)
 
 
+class KL:
+    """Kullback-Leibler divergence for probabilistic flows (the reference has it on its TensorFlow side only: voxelmorph/tf/losses.py:247-349).
+
+    `y_pred` is the 6-channel tensor [B,6,D,H,W] of VxmDenseProbabilistic: channels 0..2 the mean of the velocity field, channels 3..5
+    log sigma^2; `y_true` is not read (the reference takes only the shape from it).  The prior is the Gaussian Markov random field with precision
+    prior_lambda * (degree - adjacency) on the 6-neighbour grid; the definition is written out in include/vxm_hip.h and DESIGN.md 4.13.
+    3-D only in this version."""
+
+    def __init__(self, prior_lambda, flow_vol_shape):
+        self.prior_lambda = float(prior_lambda)
+        self.flow_vol_shape = tuple(int(s) for s in flow_vol_shape)
+        if len(self.flow_vol_shape) != 3:
+            raise ValueError("KL: 3-D volumes only in this version, got flow_vol_shape %r" % (tuple(flow_vol_shape),))
+
+    def loss(self, _, y_pred):
+        if y_pred.dim() != 5:
+            raise ValueError("KL: 3-D volumes only in this version: expected [B,6,D,H,W], got %s" % (tuple(y_pred.shape),))
+        if tuple(y_pred.shape[2:]) != self.flow_vol_shape:
+            raise ValueError("KL: y_pred lives on the grid %s, the loss was built for flow_vol_shape %s"
+                             % (tuple(y_pred.shape[2:]), self.flow_vol_shape))
+        return VF.KLFn.apply(y_pred, self.prior_lambda)
+
+
 class Dice:
     """N-D dice for segmentation (reference: losses.py:79-90)."""
 

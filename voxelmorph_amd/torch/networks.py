@@ -338,3 +338,126 @@ class VxmDenseSemiSupervisedSeg(LoadableModel):
         flow = self.register(src, trg)
         mode = 'bilinear' if interp_method == 'linear' else interp_method
         return layers.SpatialTransformer(flow.shape[2:], mode=mode).to(flow.device)(img, flow)
+
+
+class VxmDenseProbabilistic(LoadableModel):
+    """Probabilistic diffeomorphic VoxelMorph (VoxelMorph-diff): the U-Net ends in TWO 3-channel heads, the mean `flow` and the log-variance
+    `flow_logsigma` of a velocity field, trained with `losses.KL` on their concat and an image loss on a warp by a SAMPLE of that field.
+
+    The reference has this model on its TensorFlow side only (`use_probs=True`, voxelmorph/tf/networks.py:154-163, 230-232, trained by
+    scripts/tf/train.py --use-probs); its torch `VxmDense` refuses `use_probs`, and so does this package's.  This is the same wiring on the
+    torch-side API: `VxmDense`'s constructor without `use_probs`, modules `unet_model`, `flow` (N(0, 1e-5), zero bias), `flow_logsigma`
+    (N(0, 1e-10), bias -10), `resize` / `integrate` / `fullsize` / `transformer`.
+
+    forward(source, target) in training mode returns (y_source, [y_target,] flow_params) with flow_params [B,6,*inshape] = cat(mean, log sigma^2);
+    z = mean + exp(log sigma^2 / 2) * noise is resized, integrated and warped with exactly as VxmDense does with its velocity field.
+    The noise is an input of the kernels: `noise=t` uses the tensor t [B,3,*inshape] as it stands (pass `model.noise` after
+    `model.draw_noise()` for a captured step: a replay reads the buffer by address); without it `forward` draws into the static buffer
+    `model.noise` first, unless a stream capture is under way, when it reads the buffer as it stands.
+    In eval() mode or with registration=True z is the mean (the MAP field) unless sample=True.  3-D, fp32 only in this version."""
+
+    @store_config_args
+    def __init__(self, inshape, nb_unet_features=None, nb_unet_levels=None, unet_feat_mult=1, nb_unet_conv_per_level=1,
+                 int_steps=7, int_downsize=2, bidir=False, src_feats=1, trg_feats=1, unet_half_res=False):
+        super().__init__()
+        ndims = len(inshape)
+        if ndims != 3:
+            raise NotImplementedError("VxmDenseProbabilistic implements 3-D volumes in this version, got inshape %r" % (tuple(inshape),))
+        self.training = True
+        self.ndims, self.bidir = ndims, bidir
+        self._feats = (src_feats, trg_feats)
+        self.inshape = tuple(int(s) for s in inshape)
+        self.unet_model = Unet(inshape, infeats=src_feats + trg_feats, nb_features=nb_unet_features, nb_levels=nb_unet_levels,
+                               feat_mult=unet_feat_mult, nb_conv_per_level=nb_unet_conv_per_level, half_res=unet_half_res)
+        # tf/networks.py:154-163: mean ~ N(0, 1e-5) with zero bias; log sigma^2 ~ N(0, 1e-10) with bias -10 (training starts at the identity
+        # with a variance of exp(-10))
+        self.flow = _Conv3dParams(self.unet_model.final_nf, ndims, ndims)
+        self.flow_logsigma = _Conv3dParams(self.unet_model.final_nf, ndims, ndims)
+        with torch.no_grad():
+            self.flow.weight.copy_(Normal(0, 1e-5).sample(self.flow.weight.shape))
+            self.flow.bias.zero_()
+            self.flow_logsigma.weight.copy_(Normal(0, 1e-10).sample(self.flow_logsigma.weight.shape))
+            self.flow_logsigma.bias.fill_(-10.0)
+        integrating, reduced = int_steps > 0, int_downsize > 1
+        self.resize = layers.ResizeTransform(int_downsize, ndims) if (integrating and reduced and not unet_half_res) else None
+        self.fullsize = layers.ResizeTransform(1 / int_downsize, ndims) if (integrating and reduced) else None
+        self.integrate = layers.VecInt([int(extent / int_downsize) for extent in inshape], int_steps) if integrating else None
+        self.transformer = layers.SpatialTransformer(inshape)
+        self.register_buffer("noise", None, persistent=False)       # [B,3,*field grid], allocated by the first forward / draw_noise
+
+    def _noise_buffer(self, like):
+        shape = (like.shape[0], 3) + tuple(like.shape[2:])
+        if self.noise is None or tuple(self.noise.shape) != shape or self.noise.device != like.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("VxmDenseProbabilistic: the noise buffer must exist before a capture (run one eager step or draw_noise())")
+            self.noise = torch.zeros(shape, dtype=torch.float32, device=like.device)
+        return self.noise
+
+    def draw_noise(self, generator=None, batch=None):
+        """Refill the static noise buffer with N(0, 1) in place (before each replay of a captured step); returns it.  `generator`: a
+        torch.Generator of the buffer's device, or a CPU generator (drawn on the host and copied: reproducible across devices)."""
+        if self.noise is None:
+            unet_half = self.resize is None and self.fullsize is not None
+            grid = tuple(s // 2 for s in self.inshape) if unet_half else self.inshape
+            dev = self.flow.weight.device
+            self.noise = torch.zeros((int(batch or 1), 3) + grid, dtype=torch.float32, device=dev)
+        if generator is not None and generator.device.type == "cpu" and self.noise.device.type != "cpu":
+            self.noise.copy_(torch.randn(self.noise.shape, generator=generator, dtype=torch.float32))
+        else:
+            self.noise.normal_(generator=generator)
+        return self.noise
+
+    def _flow_params(self, source, target):
+        if source.dim() != 5:
+            raise NotImplementedError("VxmDenseProbabilistic implements 3-D volumes [B,C,D,H,W] in this version, got a %d-D input"
+                                      % (source.dim() - 2))
+        if VB.enabled():
+            raise NotImplementedError("VxmDenseProbabilistic runs in fp32 in this version: leave torch.autocast(bfloat16) off for this model")
+        x = VF.UnetFn.apply(self.unet_model.plan(self._feats), source, target, *self.unet_model.conv_params())
+        return VF.ProbHeadsFn.apply(x, self.flow.weight, self.flow.bias, self.flow_logsigma.weight, self.flow_logsigma.bias)
+
+    def flow_distribution(self, source, target):
+        """(mu, log_sigma): mean and log sigma^2 of the velocity field, each [B,3,*grid] (views of one tensor); exp(0.5 * log_sigma) is the
+        per-voxel standard deviation."""
+        with torch.no_grad():
+            params = self._flow_params(source, target)
+        return params[:, :3], params[:, 3:]
+
+    def forward(self, source, target, registration=False, noise=None, sample=None):
+        params = self._flow_params(source, target)
+        if sample is None:
+            sample = self.training and not registration
+        flow_params = p_s = params
+        if params.requires_grad and torch.is_grad_enabled():
+            flow_params, p_s = VF.ForkFn.apply(params)           # two consumers: the caller's KL loss and the sampler
+        if sample:
+            if noise is None:
+                noise = self._noise_buffer(params)
+                if not torch.cuda.is_current_stream_capturing():
+                    noise.normal_()
+            z = VF.SampleLogVarFn.apply(p_s, noise)
+        else:
+            z = p_s[:, :3]
+        v_int = self.resize(z) if self.resize is not None else z
+
+        def moved(image, v):
+            """as VxmDense._forward_all: (moved image, displacement or None)"""
+            if self.integrate is not None and self.fullsize is not None and self.fullsize.factor != 1:
+                low = self.integrate(v)
+                if VF.warp_up_ok(image, low) and not (registration and torch.is_grad_enabled() and low.requires_grad):
+                    if registration:
+                        return VF.WarpUpFn.apply(image, low, self.fullsize.factor, self.transformer.mode, True)
+                    return VF.WarpUpFn.apply(image, low, self.fullsize.factor, self.transformer.mode, False), None
+                disp = self.fullsize(low)
+            else:
+                disp = self.integrate(v) if self.integrate is not None else v
+                if self.integrate is not None and self.fullsize is not None:
+                    disp = self.fullsize(disp)
+            return self.transformer(image, disp), disp
+
+        moved_source, forward_disp = moved(source, v_int)
+        if registration:
+            return moved_source, forward_disp
+        if self.bidir:
+            return moved_source, moved(target, -v_int)[0], flow_params
+        return moved_source, flow_params
