@@ -676,6 +676,55 @@ int vxm_kl_bwd(const float* params, double prior_lambda, const float* gloss, flo
 int vxm_sample_logvar_fwd(const float* params, const float* eps, float* z, int B, int64_t V, void* stream);
 int vxm_sample_logvar_bwd(const float* params, const float* eps, const float* gz, float* gparams, int B, int64_t V, void* stream);
 
+/* ---- image synthesis from label maps (csrc/synth.hip): the generator of SynthMorph (Hoffmann et al., IEEE TMI 41(3), 2022), which trains a
+ * contrast-agnostic registration on images synthesised from label maps.  The reference ships the training script (scripts/tf/train_synthmorph.py)
+ * and the label-map generator (voxelmorph/generators.py:421-454); the synthesis itself is a model of another package that is not part of it.
+ * The algorithm is therefore fixed HERE, as this project's restatement; no bit parity with that package is claimed.
+ *
+ * Forward only: generation is data and carries no gradient.  Every random number is an INPUT, so every call is deterministic.  The launches
+ * allocate nothing, never synchronise and read nothing on the host; there are no floating-point atomics: results repeat bit for bit.  3-D,
+ * fp32.  B <= 65535, V = voxels per sample, 1 <= V < 2^31 (VXM_ERR_BAD_SHAPE otherwise).  All arguments are checked before any launch.
+ *
+ * draw.  labels [B,V]: label values as fp32 (as in the evaluation metrics above); labels_sorted: L strictly increasing fp32 values in DEVICE
+ * memory, 1 <= L <= VXM_SYNTH_LABELS_MAX (else VXM_ERR_UNSUPPORTED); means, stds [B,L]; noise, image [B,V].  With k the index of the voxel's
+ * label in the list (`==`: -0.0 finds 0, NaN finds nothing):
+ *     image[b,i] = means[b,k] + (stds[b,k] * noise[b,i])          a multiply, then an add, each rounded on its own
+ * and 0.0f for a label that is not in the list.  16-byte accesses where V is a multiple of 4 and the bases are 16-byte aligned, element by
+ * element otherwise and for the tail; the table of a sample is kept in LDS.  A non-finite mean, std or noise value propagates by IEEE rules
+ * to the voxels that use it.
+ *
+ * one-hot.  out_index: int32 [L] in DEVICE memory, entry k = the plane of label k, in [0, Lout), or -1 for a label that is dropped;
+ * 1 <= Lout <= VXM_ONEHOT_PLANES_MAX.  onehot [B,Lout,V]: plane out_index[k] gets 1.0f where the label is labels_sorted[k], every other
+ * plane 0.0f; a dropped or unknown label (NaN included) gives zeros in all planes.  One pass: each label is read once.
+ *
+ * blur.  x, out [B,C,D,H,W]; taps [B,3,T] in DEVICE memory: per sample and per axis; T odd, 1 <= T <= VXM_BLUR_TAPS_MAX, R = (T - 1) / 2.  A
+ * separable "same" convolution with zero padding: axis 0 (D), then axis 1 (H), then axis 2 (W), each
+ *     y[i] = sum_{t = 0 .. T-1, 0 <= i + t - R < S_a} taps[b,a,t] * x[i + t - R]
+ * accumulated in fp32 in the order t = 0, 1, ... from 0.0f, every multiply and every add rounded on its own (no FMA); a tap that falls
+ * outside the volume is skipped.  x, out and work are three different buffers; work: the byte count of the workspace query (0 for a shape
+ * the call refuses; VXM_ERR_WORKSPACE below it).  A NaN / Inf voxel reaches the voxels whose taps read it (0 * Inf = NaN included).
+ *
+ * finish.  x, out [B,V]; log_bias [B,V] or NULL; gamma [B] in DEVICE memory.
+ *     y    = fminf(fmaxf(x * expf(log_bias), 0), 255)              without the multiply when log_bias is NULL
+ *     mn, mx = the minimum and maximum of y over the sample        (per-workgroup partials in `work`, reduced in one fixed order; exact)
+ *     out  = powf((y - mn) / (mx - mn), gamma[b])                  0.0f everywhere when mx == mn; IEEE division
+ * expf / powf are the device library's functions, not the fast intrinsics; with gamma[b] == 1.0f the quotient is written as it stands (what
+ * a correctly rounded pow returns).  The second pass recomputes y from x with the same expression: y is never stored.  fmaxf / fminf drop a
+ * NaN: a NaN product counts as 0, +Inf as 255, -Inf as 0. */
+#define VXM_SYNTH_LABELS_MAX 4096
+#define VXM_ONEHOT_PLANES_MAX 256
+#define VXM_BLUR_TAPS_MAX 25
+int vxm_synth_draw_fwd(const float* labels, const float* labels_sorted, const float* means, const float* stds, const float* noise, float* image,
+                       int L, int B, int64_t V, void* stream);
+int vxm_onehot_fwd(const float* labels, const float* labels_sorted, const int* out_index, int L, int Lout, float* onehot, int B, int64_t V,
+                   void* stream);
+size_t vxm_blur3d_workspace_bytes(int T, int B, int C, int D, int H, int W);
+int vxm_blur3d_fwd(const float* x, const float* taps, int T, float* out, void* work, size_t work_bytes, int B, int C, int D, int H, int W,
+                   void* stream);
+size_t vxm_synth_finish_workspace_bytes(int B, int64_t V);
+int vxm_synth_finish_fwd(const float* x, const float* log_bias, const float* gamma, float* out, void* work, size_t work_bytes, int B, int64_t V,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,12 @@ SIGNATURES = {
     "vxm_kl_bwd": [_P, _D, _P, _P, _I, _I, _I, _I, _P],
     "vxm_sample_logvar_fwd": [_P, _P, _P, _I, _L, _P],
     "vxm_sample_logvar_bwd": [_P, _P, _P, _P, _I, _L, _P],
+    "vxm_synth_draw_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _P],
+    "vxm_onehot_fwd": [_P, _P, _P, _I, _I, _P, _I, _L, _P],
+    "vxm_blur3d_workspace_bytes": [_I, _I, _I, _I, _I, _I],
+    "vxm_blur3d_fwd": [_P, _P, _I, _P, _P, _S, _I, _I, _I, _I, _I, _P],
+    "vxm_synth_finish_workspace_bytes": [_I, _L],
+    "vxm_synth_finish_fwd": [_P, _P, _P, _P, _P, _S, _I, _L, _P],
 }
 _RESTYPES = {
     "vxm_workspace_bytes": _S,
@@ -195,6 +201,8 @@ _RESTYPES = {
     "vxm_mi_chunk": _L,
     "vxm_mi_workspace_bytes": _S,
     "vxm_kl_workspace_bytes": _S,
+    "vxm_blur3d_workspace_bytes": _S,
+    "vxm_synth_finish_workspace_bytes": _S,
 }
 
 _lib = None

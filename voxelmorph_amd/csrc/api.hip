@@ -4,7 +4,7 @@
 thread_local char vxm_err_buf[512] = "";
 
 extern "C" {
-int vxm_version(void) { return 506; }                       /* 0.5.6: probabilistic velocity field (vxm_kl_*, vxm_sample_logvar_*; additive); 0.5.5: affine matrix -> dense shift (vxm_affine_shift3d_*; additive); 0.5.4: mutual information loss (vxm_mi_*; additive); 0.5.3: evaluation metrics (label overlap, fused warp + overlap, Jacobian determinant; additive); 0.5.2: vxm_resize3d_bwd_kernel (additive query); 0.5.1: pooling codes + fused pooling backward / first weight gradient, small-volume conv kernel (additive); 0.5.0: round 6 (vecint_bwd_ws, fused upsample + warp, weighted loss finishers); 0.4.0: round 5 (capturable Adam, range probe, bwd_data / workspace_bytes names); 0.3.0: split-fp32 convs */
+int vxm_version(void) { return 507; }                       /* 0.5.7: image synthesis from label maps (vxm_synth_draw_fwd, vxm_onehot_fwd, vxm_blur3d_*, vxm_synth_finish_*; additive); 0.5.6: probabilistic velocity field (vxm_kl_*, vxm_sample_logvar_*; additive); 0.5.5: affine matrix -> dense shift (vxm_affine_shift3d_*; additive); 0.5.4: mutual information loss (vxm_mi_*; additive); 0.5.3: evaluation metrics (label overlap, fused warp + overlap, Jacobian determinant; additive); 0.5.2: vxm_resize3d_bwd_kernel (additive query); 0.5.1: pooling codes + fused pooling backward / first weight gradient, small-volume conv kernel (additive); 0.5.0: round 6 (vecint_bwd_ws, fused upsample + warp, weighted loss finishers); 0.4.0: round 5 (capturable Adam, range probe, bwd_data / workspace_bytes names); 0.3.0: split-fp32 convs */
 const char* vxm_last_error_string(void) { return vxm_err_buf; }
 
 /* convolution_backward w.r.t. the input under its SURVEY name: pack the transposed / flipped operator into the caller's scratch and run the

@@ -345,3 +345,55 @@ def scan_to_atlas(vol_names, atlas, bidir=False, batch_size=1, no_warp=False, se
 def semisupervised(vol_names, seg_names, labels, atlas_file=None, downsize=2, **kwargs):
     """Drop-in for `voxelmorph.generators.semisupervised` (generators.py:146-194) yielding device tensors."""
     return SemiSupervisedLoader(vol_names, seg_names, labels, atlas_file=atlas_file, downsize=downsize, **kwargs)
+
+
+class SynthMorphLoader:
+    """`synthmorph` (generators.py:421-454): pairs of label maps for SynthMorph training.  The pre-loaded maps are uploaded once as one
+    fp32 bank [N,1,*shape] (label values are exact in fp32 below 2^24); a batch is a device-side gather of 2 B maps, flipped together along
+    a random subset of the axes, split into source and target.  Yields `[src, trg]`, each [B,1,*shape] fp32 on the device; the reference's
+    second tuple entry (two zero arrays that the SynthMorph losses ignore) is not produced."""
+
+    def __init__(self, label_maps, batch_size=1, same_subj=False, flip=True, device=None, rank=0, seed=0):
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise ValueError('SynthMorphLoader feeds the MI355X path: device must be a HIP device, got %s' % self.device)
+        maps = [np.asarray(m) for m in label_maps]
+        if not maps:
+            raise ValueError('no label maps given')
+        shape = maps[0].shape
+        if any(m.shape != shape for m in maps):
+            raise ValueError('all label maps must share one shape, got %s' % sorted({m.shape for m in maps}))
+        if any(not np.issubdtype(m.dtype, np.integer) for m in maps) or max(int(np.abs(m).max()) for m in maps) >= 1 << 24:
+            raise ValueError('label maps must be of an integer type with values below 2^24')
+        self.shape, self.n = tuple(shape), len(maps)
+        self.batch_size, self.same_subj, self.flip = int(batch_size), bool(same_subj), bool(flip)
+        self.rng = np.random.default_rng([seed, rank])
+        self.bank = torch.from_numpy(np.stack(maps).astype(np.float32))[:, None].to(self.device)
+        self.last_indices = self.last_axes = None
+
+    def _draw(self):
+        """(indices of the 2 B maps, flipped axes) as generators.py:441-450 draws them"""
+        ind = self.rng.integers(self.n, size=2 * self.batch_size)
+        if self.same_subj:
+            ind = np.concatenate([ind[:self.batch_size]] * 2)
+        axes = np.zeros(0, dtype=np.int64)
+        if self.flip:
+            nd = len(self.shape)
+            axes = self.rng.choice(nd, size=self.rng.integers(nd + 1), replace=False, shuffle=False)
+        return ind, axes
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        ind, axes = self._draw()
+        self.last_indices, self.last_axes = ind, axes
+        x = self.bank.index_select(0, torch.from_numpy(np.asarray(ind, dtype=np.int64)).to(self.device))
+        if len(axes):
+            x = torch.flip(x, [int(a) + 2 for a in axes])
+        return [x[:self.batch_size].contiguous(), x[self.batch_size:].contiguous()]
+
+
+def synthmorph(label_maps, batch_size=1, same_subj=False, flip=True, **kwargs):
+    """Drop-in for `voxelmorph.generators.synthmorph` (generators.py:421-454) yielding device tensors `[src, trg]`."""
+    return SynthMorphLoader(label_maps, batch_size=batch_size, same_subj=same_subj, flip=flip, **kwargs)
